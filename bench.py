@@ -9,7 +9,9 @@ compress of the rank's segments into per-segment slots + the RCCL all-gather of 
 per-segment compressed sizes and the global frame index + LZ4 decompress of every slot.
 value = uncompressed bytes round-tripped by all ranks / wall time (max over ranks).
 
-Beside it, on the same JSON line:
+A plain run does only that: set up, warm up, time the K steps, write the outputs of the last
+step when --dump-outputs DIR is given, print the line.  With --full, beside the headline on
+the same JSON line:
   recordbatch   BASELINE configs[3]: an 8 GiB Arrow record-batch job (64 KiB chunks), the
                 same round-robin batches, K queue-pair streams per GPU running concurrently
                 (CompressAsync / DecompressAsync, util.h:216-236), RCCL size all-gather;
@@ -23,10 +25,20 @@ Beside it, on the same JSON line:
   cpu_baseline  stock liblz4 / zlib-1 on this host's cores, 1 core and all cores, plus
                 BASELINE configs[0] (1 MiB Arrow IPC of a Parquet-like table, 1 core).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  With --gpus N > 1 and no launcher
-around it, the process starts N rank processes itself (bitar_amd.launch; the parent never
-touches the GPU); under torch.distributed.run the ranks come from the environment.  Rank 0
-prints ONE JSON line.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  With
+--gpus N > 1 and no launcher around it, the process starts N rank processes itself
+(bitar_amd.launch; the parent never touches the GPU); under torch.distributed.run the ranks
+come from the environment.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the headline's last timed step handed its caller, as
+DIR/<name>.npy (float64, the byte samples float32; DIR/<name>_rank<r>.npy per rank when
+N > 1): `sizes` (compressed
+bytes per segment), `frame_index` (the global frame index), `produced` (decompressed bytes
+per segment), `slab_checksum` / `out_checksum` (a position-weighted byte sum of every
+segment's compressed slot and decompressed bytes), and the bytes themselves for a fixed
+sample: `slab_sample` (whole slots of DUMP_SLOTS segments, zero past each segment's size)
+and `out_sample` (DUMP_BYTES positions of the decompressed buffer).  The input is the
+deterministic generator's, so two builds run with the same arguments compare file for file.
 """
 import argparse
 import json
@@ -47,6 +59,11 @@ def parse():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--bytes", type=int, default=1 << 30, help="headline bytes per rank")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline (other codecs, inputs and "
+                        "stream counts, stock-stream decode, the C++ front-end, CPU baselines)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the outputs of the headline's last timed step as DIR/<name>.npy")
     p.add_argument("--seg", type=int, default=65536)
     p.add_argument("--kind", type=int, default=1, help="0 random, 1 mixed, 2 arrow")
     p.add_argument("--codec", default="lz4",
@@ -71,9 +88,13 @@ def parse():
     p.add_argument("--no-qp2", action="store_true",
                    help="skip the headline job over two queue-pair streams (informational)")
     p.add_argument("--only", default=None,
-                   help="comma list of legs to run besides the headline (profiling runs)")
+                   help="comma list of the --full legs to run besides the headline "
+                        "(profiling runs)")
     p.add_argument("--traffic-json", default=os.path.join(HERE, "profiles", "traffic.json"))
-    return p.parse_args()
+    args = p.parse_args()
+    if args.only is not None and not args.full:
+        p.error("--only picks among the legs of a --full run")
+    return args
 
 
 # every kernel one compress / decompress call launches (a "+" list: the HIP events bracket
@@ -127,11 +148,63 @@ def reduce_max_sum(vals_max, vals_sum, world):
     return a.tolist(), b.tolist()
 
 
+DUMP_SLOTS = 64        # segments whose whole compressed slot --dump-outputs writes
+DUMP_BYTES = 4 << 20   # positions of the decompressed buffer --dump-outputs writes
+DUMP_CHUNK = 1024      # segments per pass of the checksums (bounds their temporaries)
+
+
+def dump_outputs(job, dump_dir, world, rank):
+    """--dump-outputs: what the job's last step handed its caller (see the module docstring),
+    .npy files, ~35 MB at the headline's size and little more for a larger job."""
+    import numpy as np
+    import torch
+    L = job.layout
+    nseg, seg, stride = L.local_nseg, job.seg, job.stride
+    if nseg == 0:  # a rank without segments has no outputs
+        return
+    dev = job.out.device
+    sizes = job.sizes[:nseg].to(torch.int64)
+    produced = job.produced[:nseg].to(torch.int64)
+
+    def checksum(buf, width, lens):
+        # sum over a segment's valid bytes of byte * (1 + position % 251): below 2^53, so
+        # exact in float64
+        w = (torch.arange(width, device=dev, dtype=torch.int64) % 251) + 1
+        pos = torch.arange(width, device=dev, dtype=torch.int64)
+        res = torch.empty(nseg, dtype=torch.int64, device=dev)
+        for s in range(0, nseg, DUMP_CHUNK):
+            e = min(s + DUMP_CHUNK, nseg)
+            rows = buf[s * width:e * width].view(e - s, width).to(torch.int64)
+            rows = rows * (pos[None, :] < lens[s:e, None])
+            res[s:e] = (rows * w[None, :]).sum(dim=1)
+        return res
+
+    rng = np.random.default_rng(20240229)
+    slots = np.sort(rng.choice(nseg, size=min(DUMP_SLOTS, nseg), replace=False))
+    at = np.sort(rng.integers(0, L.local_bytes, size=min(DUMP_BYTES, L.local_bytes)))
+    slots_d = torch.from_numpy(slots).to(dev)
+    slab_sample = job.slab[:nseg * stride].view(nseg, stride)[slots_d].to(torch.int64)
+    slab_sample = slab_sample * (torch.arange(stride, device=dev)[None, :] < sizes[slots_d, None])
+    arrays = {"sizes": sizes, "produced": produced, "frame_index": job.index,
+              "slab_checksum": checksum(job.slab, stride, sizes),
+              "out_checksum": checksum(job.out, seg, produced),
+              "slab_sample_segments": torch.from_numpy(slots),
+              "slab_sample": slab_sample,
+              "out_sample": job.out[torch.from_numpy(at).to(dev)]}
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in arrays.items():
+        path = os.path.join(dump_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy")
+        # the byte samples fit float32 exactly; sums and offsets need float64
+        np.save(path, t.cpu().numpy().astype(np.float32 if name.endswith("_sample")
+                                             else np.float64))
+
+
 def run_job(eng, codec_name, kind, job_bytes, seg, nstreams, steps, warmup, world, rank,
-            seed=0):
+            seed=0, dump_dir=None):
     """K timed steps of a sharded job (bitar_amd.job.ShardedJob): compress on every part's
     stream, RCCL size all-gather + global frame index, decompress.  Returns the timings
-    (max over ranks), the byte-equality verdict (all ranks) and the job's sizes."""
+    (max over ranks), the byte-equality verdict (all ranks) and the job's sizes.  With
+    dump_dir, the last step's outputs are written there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from bitar_amd.job import ShardedJob
@@ -185,6 +258,8 @@ def run_job(eng, codec_name, kind, job_bytes, seg, nstreams, steps, warmup, worl
     local = {"nbytes": job.layout.local_bytes, "nseg": job.layout.local_nseg,
              "parts": len(job.layout.parts)}
     total_c = int(job.index[-1].item())
+    if dump_dir is not None:
+        dump_outputs(job, dump_dir, world, rank)
     job.free()
     t_comp, t_dec = sum(comp_ms) / len(comp_ms) / 1e3, sum(dec_ms) / len(dec_ms) / 1e3
     # max over ranks, and the per-rank spread (min through the max of the negation), so the
@@ -593,6 +668,10 @@ def frontend_legs(args, headline_ms):
 
 
 def want(args, leg):
+    """Does this run include `leg`?  A plain run has the headline alone; --full adds every
+    leg, or with --only the ones it lists."""
+    if not args.full:
+        return False
     if args.only is None:
         return True
     return leg in args.only.split(",")
@@ -625,7 +704,7 @@ def main():
     eng = bitar_amd.Engine(dev, num_streams=max(1, args.streams))
     n, seg = args.bytes, args.seg
     r = run_job(eng, args.codec, args.kind, world * n, seg, 1, args.steps, args.warmup, world,
-                rank)
+                rank, dump_dir=args.dump_outputs)
     rb = zs = df = None
     if not args.no_recordbatch and want(args, "recordbatch"):
         rb = run_job(eng, "lz4", 2, args.record_bytes, 65536, max(1, args.streams),
@@ -768,11 +847,12 @@ def main():
             res["stock_ratio"]["ours_lz4_wide"] = res["lz4_wide"]["compression_ratio"]
     if stock is not None:
         res["stock_decode"] = stock[0]
-    if world == 1 and args.codec == "lz4" and (args.only is None or want(args, "frontend")):
+    if world == 1 and args.codec == "lz4" and want(args, "frontend"):
         res["frontend"], hd = frontend_legs(args, res["ms_per_step"])
         if hd is not None:
             res["h2d_d2h"] = hd
-    if not args.no_cpu_baseline and world == 1 and args.codec == "lz4" and args.only is None:
+    if (args.full and not args.no_cpu_baseline and world == 1 and args.codec == "lz4"
+            and args.only is None):
         res["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(res), flush=True)
     if use_dist:

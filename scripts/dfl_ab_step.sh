@@ -13,6 +13,6 @@ for c in deflate deflate_dyn; do
 done
 for v in ${VARIANTS:-head cur}; do
   if [ "$v" = cur ]; then lib=bitar_amd/lib/libbitar_hip.so; else lib=bitar_amd/lib/variants/libbitar_hip_$v.so; fi
-  BITAR_HIP_LIB=$lib timeout -k 10 300 python bench.py --only stock --steps 10 --warmup 3 --no-cpu-baseline --no-qp2 \
+  BITAR_HIP_LIB=$lib timeout -k 10 300 python bench.py --full --only stock --steps 10 --warmup 3 --no-cpu-baseline --no-qp2 \
     > gpurun_out/bst_$v.json 2> gpurun_out/bst_$v.err || exit 1
 done

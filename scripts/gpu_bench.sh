@@ -5,6 +5,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-r01}
+# every leg of the benchmark, and --only to pick one for a profile pass, need --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
 if [ -z "$NO_BENCH" ]; then  # (NO_BENCH=1: profile passes only, e.g. a second call)
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { echo smoke failed; cat gpurun_out/smoke.log; exit 1; }
 timeout -k 10 600 python bench.py ${BENCH_ARGS} > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { echo bench failed; tail -30 gpurun_out/bench_${TAG}.err; exit 1; }

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-sq}
-if [ -n "$ARGS" ]; then PROG="scripts/prof_one.py $ARGS"; else PROG="bench.py --only headline --steps 2 --warmup 1 ${BENCH_ARGS}"; fi
+if [ -n "$ARGS" ]; then PROG="scripts/prof_one.py $ARGS"; else PROG="bench.py --steps 2 --warmup 1 ${BENCH_ARGS}"; fi
 timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SMEM SQ_INSTS_BRANCH \
   -d gpurun_out/$TAG -o pmc --output-format csv -- python3 $PROG \
   > gpurun_out/$TAG.log 2>&1 || { echo "sq pass failed"; tail -20 gpurun_out/$TAG.log; exit 1; }

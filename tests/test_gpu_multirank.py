@@ -1,4 +1,4 @@
-"""The N-rank bench path on real hardware, rehearsed on one GPU: `bench.py --gpus 2` spawns
+"""The N-rank bench path on real hardware, rehearsed on one GPU: `bench.py --gpus 2 --full` spawns
 two rank processes (bitar_amd.launch), each drives the HIP engine on the box's GPU, the
 size all-gather runs over gloo on host copies (BITAR_DIST_BACKEND=gloo; RCCL refuses two
 ranks on one device), and rank 0 prints the one JSON line.  The 8-GPU RCCL run is the
@@ -23,7 +23,7 @@ def test_bench_two_ranks_share_one_gpu():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--bytes", str(64 << 20), "--record-bytes", str(256 << 20),
-           "--only", "recordbatch,zstd,deflate"]
+           "--full", "--only", "recordbatch,zstd,deflate"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -57,7 +57,7 @@ def test_bench_one_rank_rccl_collectives():
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
            "--bytes", str(64 << 20), "--record-bytes", str(256 << 20),
-           "--only", "recordbatch,zstd", "--no-cpu-baseline"]
+           "--full", "--only", "recordbatch,zstd", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
