@@ -100,6 +100,10 @@ def lib():
         "bitar_hip_path_counters": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), u32]),
         "bitar_hip_compress_host": (i32, [vp, vp, u32, vp, u64, u32, vp, vp, vp, u64, vp]),
         "bitar_hip_decompress_host": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, u64, vp]),
+        "bitar_hip_compress_bits": (i32, [vp, vp, u32, vp, u64, u32, vp, u64, vp, vp]),
+        "bitar_hip_deflate_join": (i32, [vp, vp, vp, u64, vp, vp, u32, vp, vp, u64]),
+        "bitar_hip_deflate_split": (i32, [vp, vp, vp, u64, vp, vp, u32, vp, u64, vp]),
+        "bitar_hip_crc32_combine": (i32, [vp, vp, vp, u64, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -120,7 +124,9 @@ ABI_SYMBOLS = ("bitar_hip_abi_version", "bitar_hip_last_error", "bitar_hip_devic
                "bitar_hip_fill_at", "bitar_hip_checksum", "bitar_hip_copy_batch",
                "bitar_hip_lz4_chain", "bitar_hip_get_decoder_options",
                "bitar_hip_set_decoder_options", "bitar_hip_path_counters",
-               "bitar_hip_compress_host", "bitar_hip_decompress_host")
+               "bitar_hip_compress_host", "bitar_hip_decompress_host",
+               "bitar_hip_compress_bits", "bitar_hip_deflate_join", "bitar_hip_deflate_split",
+               "bitar_hip_crc32_combine")
 
 
 def check(rc):
@@ -271,6 +277,37 @@ class Engine:
         nseg = (n + seg - 1) // seg if nseg is None else nseg
         check(lib().bitar_hip_checksum(self.ctx, self._stream(stream), kind, _ptr(data), n, seg,
                                        _ptr(lens), nseg, _ptr(sums)))
+
+    # --- one DEFLATE stream from the segments' streams (gzip members) -------------------
+    def compress_bits_into(self, codec, data, seg, slab, stride, sizes, bits, n=None,
+                           stream=None):
+        """compress_into for the two DEFLATE codecs, + each segment's exact bit length in the
+        int32 tensor `bits` (None: exactly compress_into)"""
+        n = data.numel() * data.element_size() if n is None else n
+        check(lib().bitar_hip_compress_bits(self.ctx, self._stream(stream), codec, _ptr(data), n,
+                                            seg, _ptr(slab), stride, _ptr(sizes), _ptr(bits)))
+
+    def deflate_join(self, slab, stride, sizes, bits, nseg, starts, joined=None, capacity=None,
+                     stream=None):
+        """starts (int64 tensor, nseg + 1): each segment's bit position in the one raw DEFLATE
+        stream joined from the slots; joined (uint8 tensor or None: positions only)"""
+        # (capacity: a multiple of 4, the stream is written in whole dwords)
+        cap = (joined.numel() & ~3 if joined is not None else 0) if capacity is None else capacity
+        check(lib().bitar_hip_deflate_join(self.ctx, self._stream(stream), _ptr(slab), stride,
+                                           _ptr(sizes), _ptr(bits), nseg, _ptr(starts),
+                                           _ptr(joined), cap))
+
+    def deflate_split(self, joined, joined_len, starts, entries, nseg, slab, stride, sizes,
+                      stream=None):
+        """the inverse of deflate_join: entries (int32 tensor) = bits | stored << 23"""
+        check(lib().bitar_hip_deflate_split(self.ctx, self._stream(stream), _ptr(joined),
+                                            joined_len, _ptr(starts), _ptr(entries), nseg,
+                                            _ptr(slab), stride, _ptr(sizes)))
+
+    def crc32_combine(self, sums, n, seg, crc, stream=None):
+        """crc (int32 tensor, 1 entry) = CRC-32 of n bytes from their segments' CRC-32s"""
+        check(lib().bitar_hip_crc32_combine(self.ctx, self._stream(stream), _ptr(sums), n, seg,
+                                            (n + seg - 1) // seg, _ptr(crc)))
 
     def copy_batch(self, srcs, dsts, sizes, n, stream=None):
         """entry i: sizes[i] bytes from srcs[i] to dsts[i] (int64 / int32 device tensors)"""

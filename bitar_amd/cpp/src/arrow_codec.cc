@@ -1,7 +1,8 @@
-// arrow_codec.cc -- arrow::util::Codec adapters (ZSTD, LZ4_FRAME) over the C ABI.
+// arrow_codec.cc -- arrow::util::Codec adapters (ZSTD, LZ4_FRAME, GZIP) over the C ABI.
 // See include/bitar/arrow_codec.h for the stream layouts.  Every payload byte is compressed
-// and decompressed on the device; the host only walks frame / block headers (sizes) and
-// writes the 7-byte LZ4 frame header and EndMark.
+// and decompressed on the device; the host only walks frame / block / member headers (sizes)
+// and writes the 7-byte LZ4 frame header and EndMark, or the gzip member header and trailer
+// (gzip_frame.h).
 #include "bitar/arrow_codec.h"
 
 #include <arrow/status.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "bitar_hip.h"
+#include "gzip_frame.h"
 #include "hip_ctx.h"
 
 namespace bitar {
@@ -76,7 +78,8 @@ class HipCodec : public arrow::util::Codec {
   HipCodec(arrow::Compression::type type, int device, bitar_hip_ctx* ctx)
       : type_(type), device_(device), ctx_(ctx) {}
   ~HipCodec() override {
-    for (void* p : {d_in_, d_slab_, d_sizes_, d_off_, d_frame_, d_out_, d_srcs_, d_aux_})
+    for (void* p : {d_in_, d_slab_, d_sizes_, d_off_, d_frame_, d_out_, d_srcs_, d_aux_, d_join_,
+                    d_meta_})
       if (p) bitar_hip_free(ctx_, p);
     bitar_hip_close(ctx_);
   }
@@ -91,6 +94,10 @@ class HipCodec : public arrow::util::Codec {
     const uint64_t nseg = (static_cast<uint64_t>(input_len) + kSeg - 1) / kSeg;
     if (type_ == arrow::Compression::ZSTD)
       return static_cast<int64_t>(9 + nseg * bitar_hip_slot_size(BITAR_HIP_CODEC_ZSTD, kSeg));
+    if (type_ == arrow::Compression::GZIP)  // header + index, the joined stream, trailer
+      return static_cast<int64_t>(std::max<uint64_t>(
+          gzf::HeaderLen(nseg) + nseg * (gzf::SlotSize(kSeg) + 1) + gzf::kTrailerLen,
+          gzf::EmptyMemberLen()));
     return static_cast<int64_t>(7 + nseg * (4 + kSeg) + 4);
   }
 
@@ -135,6 +142,13 @@ class HipCodec : public arrow::util::Codec {
                                         int64_t output_buffer_len, uint8_t* output);
   arrow::Result<int64_t> DecompressLz4f(const std::vector<Frame>& frames, const uint8_t* d_in,
                                         uint64_t n, int64_t output_buffer_len, uint8_t* output);
+  arrow::Result<int64_t> CompressGzip(uint64_t n, const uint8_t* input, int64_t output_buffer_len,
+                                      uint8_t* output);
+  arrow::Result<int64_t> DecompressGzip(uint64_t n, const uint8_t* input,
+                                        int64_t output_buffer_len, uint8_t* output);
+  arrow::Status GzipIndexed(const gzf::Member& m, const uint8_t* input, uint8_t* output);
+  arrow::Status GzipSingles(const std::vector<gzf::Member>& ms, size_t m0, size_t m1,
+                            const uint8_t* d_in, uint8_t* output);
   // the frame's independent 64 KiB blocks, in parallel, to dout; returns the content size
   arrow::Result<uint64_t> Lz4Independent(const Frame& f, const uint8_t* d_in, uint8_t* dout);
 
@@ -143,9 +157,10 @@ class HipCodec : public arrow::util::Codec {
   bitar_hip_ctx* ctx_;
   std::mutex mu_;  // one stream per codec; Arrow may share a codec between threads
   void *d_in_ = nullptr, *d_slab_ = nullptr, *d_sizes_ = nullptr, *d_off_ = nullptr,
-       *d_frame_ = nullptr, *d_out_ = nullptr, *d_srcs_ = nullptr, *d_aux_ = nullptr;
+       *d_frame_ = nullptr, *d_out_ = nullptr, *d_srcs_ = nullptr, *d_aux_ = nullptr,
+       *d_join_ = nullptr, *d_meta_ = nullptr;
   uint64_t c_in_ = 0, c_slab_ = 0, c_sizes_ = 0, c_off_ = 0, c_frame_ = 0, c_out_ = 0,
-           c_srcs_ = 0, c_aux_ = 0;
+           c_srcs_ = 0, c_aux_ = 0, c_join_ = 0, c_meta_ = 0;
 };
 
 arrow::Result<int64_t> HipCodec::Compress(int64_t input_len, const uint8_t* input,
@@ -155,6 +170,7 @@ arrow::Result<int64_t> HipCodec::Compress(int64_t input_len, const uint8_t* inpu
   if (output_buffer_len < MaxCompressedLen(input_len, input))
     return arrow::Status::Invalid("output buffer smaller than MaxCompressedLen");
   const uint64_t n = static_cast<uint64_t>(input_len);
+  if (type_ == arrow::Compression::GZIP) return CompressGzip(n, input, output_buffer_len, output);
   const uint64_t nseg = (n + kSeg - 1) / kSeg;
   const bool zstd = type_ == arrow::Compression::ZSTD;
   const bool out_dev = OnDevice(output);
@@ -322,6 +338,8 @@ arrow::Result<int64_t> HipCodec::Decompress(int64_t input_len, const uint8_t* in
   const std::lock_guard<std::mutex> lock(mu_);
   if (input_len < 0 || output_buffer_len < 0) return arrow::Status::Invalid("negative length");
   const uint64_t n = static_cast<uint64_t>(input_len);
+  if (type_ == arrow::Compression::GZIP)
+    return DecompressGzip(n, input, output_buffer_len, output);
   const bool zstd = type_ == arrow::Compression::ZSTD;
   const bool in_dev = OnDevice(input);
   // the header walk needs the bytes on the host
@@ -534,13 +552,301 @@ arrow::Result<int64_t> HipCodec::DecompressLz4f(const std::vector<Frame>& frames
   return static_cast<int64_t>(total);
 }
 
+// ---- GZIP (RFC 1952; layout and index in gzip_frame.h) ----
+
+arrow::Status FromGzf(const gzf::Status& st) {
+  if (st.ok()) return arrow::Status::OK();
+  return st.code == gzf::Code::kNotImplemented ? arrow::Status::NotImplemented(st.msg)
+                                               : arrow::Status::Invalid(st.msg);
+}
+
+// One member: the segments' dynamic-Huffman streams (the reference default) joined into one
+// raw DEFLATE stream on the device, the 'BT' index of their bit lengths in FEXTRA, CRC-32 of
+// the input from its segments' CRC-32s.  Only the bit lengths, the stream's length and the
+// CRC visit the host.
+arrow::Result<int64_t> HipCodec::CompressGzip(uint64_t n, const uint8_t* input,
+                                              int64_t output_buffer_len, uint8_t* output) {
+  const bool out_dev = OnDevice(output);
+  const uint64_t nseg = (n + kSeg - 1) / kSeg;
+  if (n == 0) {
+    uint8_t empty[64];
+    static_assert(sizeof empty >= 24 + 2 + 8, "empty member");
+    gzf::WriteEmptyMember(empty);
+    const uint64_t len = gzf::EmptyMemberLen();
+    if (out_dev) {
+      ARROW_RETURN_NOT_OK(Copy(output, empty, len));
+      ARROW_RETURN_NOT_OK(Sync());
+    } else {
+      std::memcpy(output, empty, len);
+    }
+    return static_cast<int64_t>(len);
+  }
+  // never write a stream this codec could not read back in parallel
+  if (nseg > gzf::kMaxIndexSegs)
+    return arrow::Status::NotImplemented(
+        "GZIP buffers above ", uint64_t(gzf::kMaxIndexSegs) * kSeg,
+        " bytes: the segment index must fit the 16-bit XLEN of one gzip member");
+  const uint32_t codec = BITAR_HIP_CODEC_DEFLATE_DYNAMIC;
+  const uint64_t stride = bitar_hip_slot_size(codec, kSeg);
+  const uint64_t cap = (nseg * (stride + 1) + 3) & ~3ull;
+  const void* d_in = input;
+  if (!OnDevice(input)) {
+    ARROW_RETURN_NOT_OK(Reserve(d_in_, c_in_, n));
+    ARROW_RETURN_NOT_OK(Copy(d_in_, input, n));
+    d_in = d_in_;
+  }
+  ARROW_RETURN_NOT_OK(Reserve(d_slab_, c_slab_, nseg * stride));
+  ARROW_RETURN_NOT_OK(Reserve(d_sizes_, c_sizes_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_aux_, c_aux_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, (nseg + 1) * 8));
+  ARROW_RETURN_NOT_OK(Reserve(d_join_, c_join_, cap));
+  ARROW_RETURN_NOT_OK(Reserve(d_meta_, c_meta_, nseg * 8 + 8 + nseg));
+  // tables of a batched copy that gathers byte 0 of every slot (BTYPE: stored or coded)
+  ARROW_RETURN_NOT_OK(Reserve(d_srcs_, c_srcs_, nseg * (2 * sizeof(void*) + 4)));
+  auto* sizes = static_cast<uint32_t*>(d_sizes_);
+  auto* bits = static_cast<uint32_t*>(d_aux_);
+  auto* starts = static_cast<uint64_t*>(d_off_);
+  auto* sums = static_cast<uint64_t*>(d_meta_);
+  auto* d_crc = reinterpret_cast<uint32_t*>(sums + nseg);
+  const uint32_t ns = static_cast<uint32_t>(nseg);
+  BITAR_ABI(bitar_hip_compress_bits(ctx_, nullptr, codec, d_in, n, kSeg, d_slab_, stride, sizes,
+                                    bits),
+            "bitar_hip_compress_bits");
+  BITAR_ABI(bitar_hip_deflate_join(ctx_, nullptr, d_slab_, stride, sizes, bits, ns, starts,
+                                   d_join_, cap),
+            "bitar_hip_deflate_join");
+  BITAR_ABI(bitar_hip_checksum(ctx_, nullptr, BITAR_HIP_CHECKSUM_CRC32, d_in, n, kSeg, nullptr, ns,
+                               sums),
+            "bitar_hip_checksum");
+  BITAR_ABI(bitar_hip_crc32_combine(ctx_, nullptr, sums, n, kSeg, ns, d_crc),
+            "bitar_hip_crc32_combine");
+  auto* d_first = reinterpret_cast<uint8_t*>(d_crc + 2);
+  {
+    std::vector<const void*> tab(2 * nseg);
+    std::vector<uint32_t> ones(nseg, 1u);
+    for (uint64_t i = 0; i < nseg; ++i) {
+      tab[i] = static_cast<const uint8_t*>(d_slab_) + i * stride;
+      tab[nseg + i] = d_first + i;
+    }
+    auto* d_tab = static_cast<void**>(d_srcs_);
+    ARROW_RETURN_NOT_OK(Copy(d_tab, tab.data(), 2 * nseg * sizeof(void*)));
+    ARROW_RETURN_NOT_OK(Copy(d_tab + 2 * nseg, ones.data(), nseg * 4));
+    BITAR_ABI(bitar_hip_copy_batch(ctx_, nullptr, d_tab, d_tab + nseg,
+                                   reinterpret_cast<const uint32_t*>(d_tab + 2 * nseg), ns),
+              "bitar_hip_copy_batch");
+  }
+  std::vector<uint32_t> entries(nseg);
+  std::vector<uint8_t> first(nseg);
+  uint64_t end_bits = 0;
+  uint32_t crc = 0;
+  ARROW_RETURN_NOT_OK(Copy(entries.data(), bits, nseg * 4));
+  ARROW_RETURN_NOT_OK(Copy(first.data(), d_first, nseg));
+  ARROW_RETURN_NOT_OK(Copy(&end_bits, starts + nseg, 8));
+  ARROW_RETURN_NOT_OK(Copy(&crc, d_crc, 4));
+  ARROW_RETURN_NOT_OK(Sync());
+  for (uint64_t i = 0; i < nseg; ++i) {
+    if (entries[i] == 0 || entries[i] > gzf::kBitsMask)
+      return arrow::Status::IOError("segment ", i, " failed to compress");
+    if ((first[i] & 6u) == 0) entries[i] |= gzf::kStoredBit;  // BTYPE 00, as the join reads it
+  }
+  const uint64_t head = gzf::HeaderLen(nseg), body = (end_bits + 7) / 8;
+  const uint64_t total = head + body + gzf::kTrailerLen;
+  if (total > static_cast<uint64_t>(output_buffer_len))
+    return arrow::Status::CapacityError("compressed stream exceeds the output buffer");
+  std::vector<uint8_t> hdr(head);
+  gzf::WriteHeader(kSeg, ns, entries.data(), hdr.data());
+  uint8_t trailer[8];
+  gzf::Wr32(trailer, crc);
+  gzf::Wr32(trailer + 4, static_cast<uint32_t>(n));
+  if (out_dev) {
+    ARROW_RETURN_NOT_OK(Copy(output, hdr.data(), head));
+    ARROW_RETURN_NOT_OK(Copy(output + head + body, trailer, 8));
+  } else {
+    std::memcpy(output, hdr.data(), head);
+    std::memcpy(output + head + body, trailer, 8);
+  }
+  ARROW_RETURN_NOT_OK(Copy(output + head, d_join_, body));
+  ARROW_RETURN_NOT_OK(Sync());
+  return static_cast<int64_t>(total);
+}
+
+// An indexed member: split the joined stream back into slots, inflate them in parallel,
+// check sizes and the CRC-32, copy the content out.
+arrow::Status HipCodec::GzipIndexed(const gzf::Member& m, const uint8_t* input, uint8_t* output) {
+  if (m.nseg == 0) return arrow::Status::OK();
+  const uint64_t nseg = m.nseg, stride = bitar_hip_slot_size(BITAR_HIP_CODEC_DEFLATE, m.seg);
+  ARROW_RETURN_NOT_OK(Reserve(d_join_, c_join_, m.deflate_len + 16));
+  ARROW_RETURN_NOT_OK(Reserve(d_slab_, c_slab_, nseg * stride));
+  ARROW_RETURN_NOT_OK(Reserve(d_sizes_, c_sizes_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_aux_, c_aux_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, (nseg + 1) * 8));
+  ARROW_RETURN_NOT_OK(Reserve(d_out_, c_out_, nseg * m.seg));
+  ARROW_RETURN_NOT_OK(Reserve(d_meta_, c_meta_, nseg * 8 + 8 + nseg * 4));
+  auto* sums = static_cast<uint64_t*>(d_meta_);
+  auto* d_crc = reinterpret_cast<uint32_t*>(sums + nseg);
+  auto* d_prod = d_crc + 2;
+  auto* dout = static_cast<uint8_t*>(d_out_);
+  // (the stream starts wherever the header ends: the split wants it 4-B aligned)
+  ARROW_RETURN_NOT_OK(Copy(d_join_, input + m.deflate_off, m.deflate_len));
+  ARROW_RETURN_NOT_OK(Copy(d_off_, m.starts.data(), (nseg + 1) * 8));
+  ARROW_RETURN_NOT_OK(Copy(d_aux_, m.entries.data(), nseg * 4));
+  BITAR_ABI(bitar_hip_deflate_split(ctx_, nullptr, d_join_, m.deflate_len,
+                                    static_cast<const uint64_t*>(d_off_),
+                                    static_cast<const uint32_t*>(d_aux_), m.nseg, d_slab_, stride,
+                                    static_cast<uint32_t*>(d_sizes_)),
+            "bitar_hip_deflate_split");
+  BITAR_ABI(bitar_hip_decompress_slab(ctx_, nullptr, BITAR_HIP_CODEC_DEFLATE_DYNAMIC, d_slab_,
+                                      stride, static_cast<const uint32_t*>(d_sizes_), m.nseg,
+                                      m.seg, dout, nseg * m.seg, d_prod),
+            "bitar_hip_decompress_slab");
+  BITAR_ABI(bitar_hip_checksum(ctx_, nullptr, BITAR_HIP_CHECKSUM_CRC32, dout, m.isize, m.seg,
+                               nullptr, m.nseg, sums),
+            "bitar_hip_checksum");
+  BITAR_ABI(bitar_hip_crc32_combine(ctx_, nullptr, sums, m.isize, m.seg, m.nseg, d_crc),
+            "bitar_hip_crc32_combine");
+  std::vector<uint32_t> prod(nseg);
+  uint32_t crc = 0;
+  ARROW_RETURN_NOT_OK(Copy(prod.data(), d_prod, nseg * 4));
+  ARROW_RETURN_NOT_OK(Copy(&crc, d_crc, 4));
+  ARROW_RETURN_NOT_OK(Sync());  // (a segment that failed to inflate: IOError here)
+  for (uint64_t i = 0; i < nseg; ++i)
+    if (prod[i] != std::min<uint64_t>(m.seg, m.isize - i * m.seg))
+      return arrow::Status::IOError("gzip segment ", i, " decoded to a wrong size");
+  if (crc != m.crc) return arrow::Status::IOError("gzip CRC-32 mismatch");
+  ARROW_RETURN_NOT_OK(Copy(output, dout, m.isize));
+  return Sync();
+}
+
+// Members ms[m0, m1) without an index (ISIZE <= 64 KiB each: small stock members, BGZF
+// blocks): one segment each, one launch.
+arrow::Status HipCodec::GzipSingles(const std::vector<gzf::Member>& ms, size_t m0, size_t m1,
+                                    const uint8_t* d_in, uint8_t* output) {
+  const uint64_t nseg = m1 - m0;
+  std::vector<const uint8_t*> srcs(nseg);
+  std::vector<uint32_t> csz(nseg);
+  for (uint64_t i = 0; i < nseg; ++i) {
+    const gzf::Member& m = ms[m0 + i];
+    if (m.deflate_len > 0xFFFFFFFFull) return arrow::Status::Invalid("gzip member over 4 GiB");
+    srcs[i] = d_in + m.deflate_off;
+    csz[i] = static_cast<uint32_t>(m.deflate_len);
+  }
+  ARROW_RETURN_NOT_OK(Reserve(d_srcs_, c_srcs_, nseg * sizeof(void*)));
+  ARROW_RETURN_NOT_OK(Reserve(d_sizes_, c_sizes_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_out_, c_out_, nseg * kSeg));
+  ARROW_RETURN_NOT_OK(Reserve(d_meta_, c_meta_, nseg * 8 + nseg * 4));
+  // the members' contents are gathered back to back on the device (one batched copy: a BGZF
+  // file has one member per 64 KiB) and leave in one copy; ISIZE <= 64 KiB each (gzf::Walk)
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < nseg; ++i) total += ms[m0 + i].isize;
+  ARROW_RETURN_NOT_OK(Reserve(d_join_, c_join_, total + 16));
+  ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, nseg * (2 * sizeof(void*) + 4)));
+  auto* sums = static_cast<uint64_t*>(d_meta_);
+  auto* d_prod = reinterpret_cast<uint32_t*>(sums + nseg);
+  auto* dout = static_cast<uint8_t*>(d_out_);
+  ARROW_RETURN_NOT_OK(Copy(d_srcs_, srcs.data(), nseg * sizeof(void*)));
+  ARROW_RETURN_NOT_OK(Copy(d_sizes_, csz.data(), nseg * 4));
+  BITAR_ABI(bitar_hip_decompress(ctx_, nullptr, BITAR_HIP_CODEC_DEFLATE_DYNAMIC,
+                                 reinterpret_cast<const void* const*>(d_srcs_),
+                                 static_cast<const uint32_t*>(d_sizes_),
+                                 static_cast<uint32_t>(nseg), kSeg, dout, nseg * kSeg, d_prod),
+            "bitar_hip_decompress");
+  BITAR_ABI(bitar_hip_checksum(ctx_, nullptr, BITAR_HIP_CHECKSUM_CRC32, dout, nseg * kSeg, kSeg,
+                               d_prod, static_cast<uint32_t>(nseg), sums),
+            "bitar_hip_checksum");
+  {
+    std::vector<const void*> tab(2 * nseg);
+    std::vector<uint32_t> len(nseg);
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < nseg; ++i) {
+      tab[i] = dout + i * kSeg;
+      tab[nseg + i] = static_cast<uint8_t*>(d_join_) + at;
+      len[i] = ms[m0 + i].isize;
+      at += len[i];
+    }
+    auto* d_tab = static_cast<void**>(d_off_);
+    ARROW_RETURN_NOT_OK(Copy(d_tab, tab.data(), 2 * nseg * sizeof(void*)));
+    ARROW_RETURN_NOT_OK(Copy(d_tab + 2 * nseg, len.data(), nseg * 4));
+    BITAR_ABI(bitar_hip_copy_batch(ctx_, nullptr, d_tab, d_tab + nseg,
+                                   reinterpret_cast<const uint32_t*>(d_tab + 2 * nseg),
+                                   static_cast<uint32_t>(nseg)),
+              "bitar_hip_copy_batch");
+  }
+  std::vector<uint32_t> prod(nseg);
+  std::vector<uint64_t> crcs(nseg);
+  ARROW_RETURN_NOT_OK(Copy(prod.data(), d_prod, nseg * 4));
+  ARROW_RETURN_NOT_OK(Copy(crcs.data(), sums, nseg * 8));
+  ARROW_RETURN_NOT_OK(Sync());
+  for (uint64_t i = 0; i < nseg; ++i) {
+    const gzf::Member& m = ms[m0 + i];
+    if (prod[i] != m.isize) return arrow::Status::IOError("gzip member decoded to a wrong size");
+    if (static_cast<uint32_t>(crcs[i]) != m.crc)
+      return arrow::Status::IOError("gzip CRC-32 mismatch");
+  }
+  ARROW_RETURN_NOT_OK(Copy(output, d_join_, total));
+  return Sync();
+}
+
+arrow::Result<int64_t> HipCodec::DecompressGzip(uint64_t n, const uint8_t* input,
+                                                int64_t output_buffer_len, uint8_t* output) {
+  const bool in_dev = OnDevice(input);
+  std::vector<uint8_t> host;  // the member walk needs the bytes on the host
+  const uint8_t* hp = input;
+  if (in_dev) {
+    host.resize(n);
+    ARROW_RETURN_NOT_OK(Copy(host.data(), input, n));
+    ARROW_RETURN_NOT_OK(Sync());
+    hp = host.data();
+  }
+  std::vector<gzf::Member> ms;
+  ARROW_RETURN_NOT_OK(FromGzf(gzf::Walk(hp, n, &ms)));
+  // ISIZE comes from untrusted trailers: the sum must fit the caller's buffer before
+  // anything is reserved
+  uint64_t declared = 0;
+  bool singles = false;
+  for (const gzf::Member& m : ms) {
+    declared += m.isize;
+    singles = singles || !m.indexed;
+    if (declared > static_cast<uint64_t>(output_buffer_len))
+      return arrow::Status::Invalid("declared gzip content exceeds the output buffer (",
+                                    output_buffer_len, ")");
+  }
+  const uint8_t* d_in = input;
+  if (singles && !in_dev) {
+    ARROW_RETURN_NOT_OK(Reserve(d_in_, c_in_, n + 16));
+    ARROW_RETURN_NOT_OK(Copy(d_in_, input, n));
+    d_in = static_cast<const uint8_t*>(d_in_);
+  }
+  constexpr size_t kBatch = 8192;  // 512 MiB of staging per launch of small members
+  uint64_t total = 0;
+  for (size_t k = 0; k < ms.size();) {
+    if (ms[k].indexed) {
+      ARROW_RETURN_NOT_OK(GzipIndexed(ms[k], input, output + total));
+      total += ms[k].isize;
+      ++k;
+      continue;
+    }
+    size_t k1 = k;
+    uint64_t bytes = 0;
+    while (k1 < ms.size() && !ms[k1].indexed && k1 - k < kBatch) bytes += ms[k1++].isize;
+    ARROW_RETURN_NOT_OK(GzipSingles(ms, k, k1, d_in, output + total));
+    total += bytes;
+    k = k1;
+  }
+  return static_cast<int64_t>(total);
+}
+
 }  // namespace
 
 arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowCodec(arrow::Compression::type type,
                                                                   int device) {
-  if (type != arrow::Compression::ZSTD && type != arrow::Compression::LZ4_FRAME)
+  if (type != arrow::Compression::ZSTD && type != arrow::Compression::LZ4_FRAME &&
+      type != arrow::Compression::GZIP)
     return arrow::Status::NotImplemented("HIP codec for ",
                                          arrow::util::Codec::GetCodecAsString(type));
+  // gzip_frame.h restates the engine's DEFLATE slot size (it includes no engine header)
+  for (uint32_t seg : {1u, 13u, 59460u, 65536u})
+    if (gzf::SlotSize(seg) != bitar_hip_slot_size(BITAR_HIP_CODEC_DEFLATE_DYNAMIC, seg))
+      return arrow::Status::UnknownError("gzip_frame.h and the engine disagree on the slot size");
   bitar_hip_config cfg{1, 0};
   bitar_hip_ctx* ctx = nullptr;
   BITAR_ABI(bitar_hip_open(device, &cfg, &ctx), "bitar_hip_open");

@@ -9,37 +9,10 @@
 // its chunk (CRC32 with a 1 KiB LDS table; Adler32 as plain and position-weighted sums), and
 // the chunks are combined in GF(2) (crc(A||B) = x^(8|B|) * crc(A) + crc(B) mod P, zlib's
 // crc32_combine) and modulo 65521.
+#include "crc32.hip.h"
 #include "wave.hip.h"
 
 namespace bitar_hip {
-
-namespace cks {
-
-constexpr uint32_t kPoly = 0xEDB88320u;  // reflected CRC-32 (zlib)
-constexpr uint32_t kBase = 65521u;       // Adler-32 modulus
-
-// a * b mod P in the reflected representation (zlib multmodp)
-__device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-  for (uint32_t m = 1u << 31; m; m >>= 1) {
-    if (a & m) p ^= b;
-    b = b & 1u ? (b >> 1) ^ kPoly : b >> 1;
-  }
-  return p;
-}
-// x^(8 n) mod P
-__device__ __forceinline__ uint32_t x8nmodp(uint32_t n) {
-  uint32_t p = 1u << 31;    // x^0
-  uint32_t sq = 1u << 23;   // x^8
-  while (n) {
-    if (n & 1u) p = multmodp(sq, p);
-    sq = multmodp(sq, sq);
-    n >>= 1;
-  }
-  return p;
-}
-
-}  // namespace cks
 
 // kind: 1 CRC32, 2 Adler32, 3 both (CRC32 | Adler32 << 32).  Segment i: lens ? lens[i] bytes
 // (BITAR_HIP_SEGMENT_ERROR -> sum 0) : min(seg, n - i*seg) bytes, at data + i*seg.

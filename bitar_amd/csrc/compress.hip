@@ -612,10 +612,15 @@ template __global__ void lz4_compress_kernel<16384, 12>(
     const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*, uint32_t*,
     const uint32_t*);
 
-__global__ __launch_bounds__(64) void deflate_compress_kernel(
+// BITS: also store the segment's exact bit length (bitar_hip_compress_bits).  Two kernels share
+// this body, so that bitar_hip_compress keeps the code it had before bits[] existed (with the
+// extra argument in its kernel the fixed-Huffman compress measured 2-3 % slower).
+template <bool BITS>
+__device__ __forceinline__ void deflate_compress_body(
     const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg,
     uint8_t* __restrict__ slab, uint64_t slot_stride, uint8_t* const* __restrict__ dsts,
-    uint32_t* __restrict__ sizes, uint32_t* __restrict__ err, const uint32_t* __restrict__ order) {
+    uint32_t* __restrict__ sizes, uint32_t* __restrict__ err, const uint32_t* __restrict__ order,
+    uint32_t* __restrict__ bits) {
   using namespace cmp;
   __shared__ __attribute__((aligned(16))) uint16_t table[1u << kHashLog];
   __shared__ __attribute__((aligned(16))) uint8_t inring[kIn + kInPad];
@@ -656,6 +661,11 @@ __global__ __launch_bounds__(64) void deflate_compress_kernel(
   // its decode launch) -- blocks of <= 65535 bytes, the last one final (oracle
   // bo_deflate_fixed_block, BO_STORE_MARGIN)
   uint32_t size = (uint32_t)((o.bits + 7) >> 3);
+  // (bits[]: what a bit-level join of the segments needs, deflate_join.hip -- a coded segment
+  // is exactly ONE block with BFINAL at bit 0 of byte 0, o.bits long including its
+  // end-of-block code; a stored segment is ceil(n / 65535) byte-aligned stored blocks, only
+  // the last one's header byte is 1)
+  uint32_t nbits = (uint32_t)o.bits;
   const uint32_t nblk = (n + 65534u) / 65535u;
   const uint32_t stored = nblk * 5u + n;
   if (!o.overflow && stored < size + (n >> 4)) {  // (oracle BO_STORE_MARGIN)
@@ -675,11 +685,30 @@ __global__ __launch_bounds__(64) void deflate_compress_kernel(
       q += 5 + len;
     }
     size = stored;
+    nbits = stored * 8u;
   }
   if (lane_id() == 0) {
     sizes[i_seg] = o.overflow ? 0xFFFFFFFFu : size;
+    if (BITS && bits) bits[i_seg] = o.overflow ? 0xFFFFFFFFu : nbits;
     if (o.overflow) atomicOr(err, 2u);
   }
+}
+
+__global__ __launch_bounds__(64) void deflate_compress_kernel(
+    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg,
+    uint8_t* __restrict__ slab, uint64_t slot_stride, uint8_t* const* __restrict__ dsts,
+    uint32_t* __restrict__ sizes, uint32_t* __restrict__ err, const uint32_t* __restrict__ order) {
+  deflate_compress_body<false>(input, n_total, seg, slab, slot_stride, dsts, sizes, err, order,
+                               nullptr);
+}
+
+__global__ __launch_bounds__(64) void deflate_compress_bits_kernel(
+    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg,
+    uint8_t* __restrict__ slab, uint64_t slot_stride, uint8_t* const* __restrict__ dsts,
+    uint32_t* __restrict__ sizes, uint32_t* __restrict__ err, const uint32_t* __restrict__ order,
+    uint32_t* __restrict__ bits) {
+  deflate_compress_body<true>(input, n_total, seg, slab, slot_stride, dsts, sizes, err, order,
+                              bits);
 }
 
 }  // namespace bitar_hip

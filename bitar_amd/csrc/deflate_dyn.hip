@@ -600,7 +600,7 @@ __global__ __launch_bounds__(64) void deflate_dyn_emit_kernel(
     const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg,
     const uint8_t* __restrict__ scratch, uint64_t scr_stride, uint8_t* __restrict__ slab,
     uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes,
-    uint32_t* __restrict__ err, const uint32_t* __restrict__ order) {
+    uint32_t* __restrict__ err, const uint32_t* __restrict__ order, uint32_t* __restrict__ bits) {
   using namespace dyn;
   __shared__ uint32_t hist[kNLit + kNDist];
   __shared__ uint32_t ltab[288];
@@ -633,7 +633,10 @@ __global__ __launch_bounds__(64) void deflate_dyn_emit_kernel(
   const GMEM uint32_t* plan = reinterpret_cast<const GMEM uint32_t*>(scr);
   GMEM uint8_t* dst = global_ptr(dsts ? dsts[i_seg] : slab + (uint64_t)i_seg * slot_stride);
   if (plan[kPlanRecBytes] == 0xFFFFFFFFu) {  // pass 1 overflowed its record area
-    if (lane == 0) sizes[i_seg] = 0xFFFFFFFFu;
+    if (lane == 0) {
+      sizes[i_seg] = 0xFFFFFFFFu;
+      if (bits) bits[i_seg] = 0xFFFFFFFFu;
+    }
     return;
   }
   for (uint32_t k = lane; k < kNLit + kNDist; k += kWave) hist[k] = plan[k];
@@ -705,7 +708,11 @@ __global__ __launch_bounds__(64) void deflate_dyn_emit_kernel(
 
   if (mode == 0) {  // stored blocks of <= 65535 bytes
     if (stored > slot_stride) {
-      if (lane == 0) { sizes[i_seg] = 0xFFFFFFFFu; atomicOr(err, 2u); }
+      if (lane == 0) {
+        sizes[i_seg] = 0xFFFFFFFFu;
+        if (bits) bits[i_seg] = 0xFFFFFFFFu;
+        atomicOr(err, 2u);
+      }
       return;
     }
     uint32_t p = 0, o = 0;
@@ -718,7 +725,13 @@ __global__ __launch_bounds__(64) void deflate_dyn_emit_kernel(
       o += 5 + len;
       p += len;
     }
-    if (lane == 0) sizes[i_seg] = o;
+    // (bits[]: a stored segment is nblk byte-aligned stored blocks, only the last one's
+    // header byte is 1; a coded one, below, is exactly ONE block with BFINAL at bit 0 of byte
+    // 0 and o.bits long including its end-of-block code -- what deflate_join.hip relies on)
+    if (lane == 0) {
+      sizes[i_seg] = o;
+      if (bits) bits[i_seg] = o * 8u;
+    }
     return;
   }
   // codes
@@ -938,6 +951,7 @@ __global__ __launch_bounds__(64) void deflate_dyn_emit_kernel(
   o.flush_words((uint32_t)((o.bits + 31) >> 5));
   if (lane == 0) {
     sizes[i_seg] = o.overflow ? 0xFFFFFFFFu : (uint32_t)((o.bits + 7) >> 3);
+    if (bits) bits[i_seg] = o.overflow ? 0xFFFFFFFFu : (uint32_t)o.bits;
     if (o.overflow) atomicOr(err, 2u);
   }
 }

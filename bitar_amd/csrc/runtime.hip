@@ -34,6 +34,9 @@ __global__ void order_scatter_kernel(const uint32_t*, const uint32_t*, uint32_t,
                                      uint32_t, const uint32_t*, uint32_t*);
 __global__ void deflate_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
                                         uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
+__global__ void deflate_compress_bits_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                             uint64_t, uint8_t* const*, uint32_t*, uint32_t*,
+                                             const uint32_t*, uint32_t*);
 __global__ void inflate_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                uint32_t*, uint32_t, unsigned long long*, const uint32_t*);
@@ -79,7 +82,14 @@ __global__ void deflate_dyn_parse_kernel(const uint8_t*, uint64_t, uint32_t, uin
                                          uint32_t*, const uint32_t*);
 __global__ void deflate_dyn_emit_kernel(const uint8_t*, uint64_t, uint32_t, const uint8_t*,
                                         uint64_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*,
-                                        uint32_t*, const uint32_t*);
+                                        uint32_t*, const uint32_t*, uint32_t*);
+__global__ void join_scan_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint32_t*,
+                                 uint32_t, uint64_t, uint64_t*, uint32_t*);
+__global__ void deflate_join_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint32_t*,
+                                    uint32_t, const uint64_t*, uint32_t*, uint64_t);
+__global__ void deflate_split_kernel(const uint8_t*, uint64_t, const uint64_t*, const uint32_t*,
+                                     uint32_t, uint8_t*, uint64_t, uint32_t*, uint32_t*);
+__global__ void crc32_combine_kernel(const uint64_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
 __global__ void checksum_kernel(uint32_t, const uint8_t*, uint64_t, uint32_t, const uint32_t*,
                                 uint32_t, uint64_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
@@ -206,7 +216,8 @@ uint32_t* err_word(bitar_hip_ctx* ctx, hipStream_t stream) {
 int sync_error(uint32_t err) {
   if (!err) return 0;
   if (err & 2u) return fail(BITAR_HIP_IO_ERROR, "Compress data output is larger than allocated buffer");
-  if (err & 4u) return fail(BITAR_HIP_IO_ERROR, "pack: a segment's size exceeds its slot (failed op)");
+  if (err & 4u)
+    return fail(BITAR_HIP_IO_ERROR, "pack / join: a segment's size exceeds its slot (failed op)");
   return fail(BITAR_HIP_IO_ERROR, "Some operations have failed");
 }
 
@@ -474,7 +485,7 @@ static void free_order_scratch(bitar_hip_ctx* ctx) {
 
 static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const void* d_in,
                          uint64_t n, uint32_t seg, void* d_slab, uint64_t slot_stride,
-                         void* const* d_dsts, uint32_t* d_sizes) {
+                         void* const* d_dsts, uint32_t* d_sizes, uint32_t* d_bits = nullptr) {
   if (int r = enter(ctx)) return r;
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
@@ -518,8 +529,13 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   else if (codec == BITAR_HIP_CODEC_DEFLATE) {
     SegOrder ord;
     if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
-    hipLaunchKernelGGL(bitar_hip::deflate_compress_kernel, dim3((uint32_t)nseg), dim3(64), 0, s,
-                       in, n, seg, slab, slot_stride, dsts, d_sizes, err_word(ctx, s), ord.order);
+    if (d_bits)  // (a kernel of its own: bitar_hip_compress keeps its code, compress.hip)
+      hipLaunchKernelGGL(bitar_hip::deflate_compress_bits_kernel, dim3((uint32_t)nseg), dim3(64),
+                         0, s, in, n, seg, slab, slot_stride, dsts, d_sizes, err_word(ctx, s),
+                         ord.order, d_bits);
+    else
+      hipLaunchKernelGGL(bitar_hip::deflate_compress_kernel, dim3((uint32_t)nseg), dim3(64), 0, s,
+                         in, n, seg, slab, slot_stride, dsts, d_sizes, err_word(ctx, s), ord.order);
     if (int r = ord.release()) return r;
   }
   else if (codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC) {
@@ -547,7 +563,8 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
                          in + cb, nb, seg, scr, scr_stride, err_word(ctx, s), ord.order);
       hipLaunchKernelGGL(bitar_hip::deflate_dyn_emit_kernel, dim3((uint32_t)cn), dim3(64), 0, s,
                          in + cb, nb, seg, static_cast<const uint8_t*>(scr), scr_stride, cslab,
-                         slot_stride, cdsts, d_sizes + c0, err_word(ctx, s), ord.order);
+                         slot_stride, cdsts, d_sizes + c0, err_word(ctx, s), ord.order,
+                         d_bits ? d_bits + c0 : nullptr);
       if (int r = ord.release()) return r;
     }
     const hipError_t le = hipGetLastError();
@@ -616,6 +633,90 @@ int bitar_hip_compress_scattered(bitar_hip_ctx* ctx, void* stream, uint32_t code
   if (n && !d_dsts) return fail(BITAR_HIP_INVALID, "null d_dsts");
   return compress_impl(ctx, stream, codec, d_in, n, seg, nullptr, slot_capacity, d_dsts,
                        d_sizes);
+}
+
+int bitar_hip_compress_bits(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const void* d_in,
+                            uint64_t n, uint32_t seg, void* d_slab, uint64_t slot_stride,
+                            uint32_t* d_sizes, uint32_t* d_bits) {
+  if (codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC)
+    return fail(BITAR_HIP_INVALID, "bit lengths exist for DEFLATE and DEFLATE_DYNAMIC only");
+  if (n && !d_slab) return fail(BITAR_HIP_INVALID, "null d_slab");
+  return compress_impl(ctx, stream, codec, d_in, n, seg, d_slab, slot_stride, nullptr, d_sizes,
+                       d_bits);
+}
+
+int bitar_hip_deflate_join(bitar_hip_ctx* ctx, void* stream, const void* d_slab,
+                           uint64_t slot_stride, const uint32_t* d_sizes, const uint32_t* d_bits,
+                           uint32_t nseg, uint64_t* d_starts, void* d_joined, uint64_t capacity) {
+  if (int r = enter(ctx)) return r;
+  if (!d_starts) return fail(BITAR_HIP_INVALID, "null d_starts");
+  if (nseg > 0x7FFFFFFFu) return fail(BITAR_HIP_INVALID, "too many segments");
+  // (whole dwords are stored and OR-ed: the last one must lie inside the capacity)
+  if (d_joined && (((uintptr_t)d_joined & 3u) != 0 || (capacity & 3u) != 0))
+    return fail(BITAR_HIP_INVALID, "d_joined must be 4-B aligned and capacity a multiple of 4");
+  if (nseg) {
+    if (!d_slab || !d_sizes || !d_bits) return fail(BITAR_HIP_INVALID, "null buffer");
+    if (((uintptr_t)d_slab & 15u) != 0 || (slot_stride & 15u) != 0 || slot_stride == 0)
+      return fail(BITAR_HIP_INVALID, "d_slab and slot_stride must be 16-B aligned");
+  }
+  hipStream_t s = pick_stream(ctx, stream);
+  // the joined stream is OR-ed into zeros at its segments' shared dwords (deflate_join.hip)
+  if (d_joined && capacity) HIP_TRY(hipMemsetAsync(d_joined, 0, capacity, s), "clear joined stream");
+  if (nseg == 0) {
+    HIP_TRY(hipMemsetAsync(d_starts, 0, sizeof(uint64_t), s), "clear starts");
+    return 0;
+  }
+  const auto* slab = static_cast<const uint8_t*>(d_slab);
+  hipLaunchKernelGGL(bitar_hip::join_scan_kernel, dim3(1), dim3(512), 0, s, slab, slot_stride,
+                     d_sizes, d_bits, nseg, d_joined ? capacity : ~0ull, d_starts,
+                     err_word(ctx, s));
+  HIP_TRY(hipGetLastError(), "join scan launch");
+  if (d_joined) {
+    hipLaunchKernelGGL(bitar_hip::deflate_join_kernel, dim3(nseg), dim3(64), 0, s, slab,
+                       slot_stride, d_sizes, d_bits, nseg, d_starts,
+                       static_cast<uint32_t*>(d_joined), capacity);
+    HIP_TRY(hipGetLastError(), "join launch");
+  }
+  return 0;
+}
+
+int bitar_hip_deflate_split(bitar_hip_ctx* ctx, void* stream, const void* d_joined,
+                            uint64_t joined_len, const uint64_t* d_starts,
+                            const uint32_t* d_entries, uint32_t nseg, void* d_slab,
+                            uint64_t slot_stride, uint32_t* d_sizes) {
+  if (int r = enter(ctx)) return r;
+  if (nseg == 0) return 0;
+  if (nseg > 0x7FFFFFFFu) return fail(BITAR_HIP_INVALID, "too many segments");
+  if (!d_joined || !d_starts || !d_entries || !d_slab || !d_sizes)
+    return fail(BITAR_HIP_INVALID, "null buffer");
+  if (((uintptr_t)d_joined & 3u) != 0) return fail(BITAR_HIP_INVALID, "d_joined must be 4-B aligned");
+  if (joined_len >> 60) return fail(BITAR_HIP_INVALID, "joined_len out of range");
+  if (((uintptr_t)d_slab & 15u) != 0 || (slot_stride & 15u) != 0 || slot_stride == 0)
+    return fail(BITAR_HIP_INVALID, "d_slab and slot_stride must be 16-B aligned");
+  hipStream_t s = pick_stream(ctx, stream);
+  hipLaunchKernelGGL(bitar_hip::deflate_split_kernel, dim3(nseg), dim3(64), 0, s,
+                     static_cast<const uint8_t*>(d_joined), joined_len, d_starts, d_entries, nseg,
+                     static_cast<uint8_t*>(d_slab), slot_stride, d_sizes, err_word(ctx, s));
+  HIP_TRY(hipGetLastError(), "split launch");
+  return 0;
+}
+
+int bitar_hip_crc32_combine(bitar_hip_ctx* ctx, void* stream, const uint64_t* d_sums, uint64_t n,
+                            uint32_t seg, uint32_t nseg, uint32_t* d_crc) {
+  if (int r = enter(ctx)) return r;
+  if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
+  if ((uint64_t)nseg != (n + seg - 1) / seg)
+    return fail(BITAR_HIP_INVALID, "nseg must be ceil(n / seg)");
+  if (!d_crc || (nseg && !d_sums)) return fail(BITAR_HIP_INVALID, "null buffer");
+  hipStream_t s = pick_stream(ctx, stream);
+  if (nseg == 0) {  // the CRC-32 of nothing
+    HIP_TRY(hipMemsetAsync(d_crc, 0, sizeof(uint32_t), s), "clear crc");
+    return 0;
+  }
+  hipLaunchKernelGGL(bitar_hip::crc32_combine_kernel, dim3(1), dim3(256), 0, s, d_sums, n, seg,
+                     nseg, d_crc);
+  HIP_TRY(hipGetLastError(), "crc combine launch");
+  return 0;
 }
 
 int bitar_hip_pointer_info(const void* ptr, int* kind, int* device) {

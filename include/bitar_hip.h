@@ -270,6 +270,53 @@ int bitar_hip_checksum(bitar_hip_ctx* ctx, void* stream, uint32_t kind, const vo
                        uint64_t n, uint32_t seg, const uint32_t* d_lens, uint32_t nseg,
                        uint64_t* d_sums);
 
+/* ---- one gzip member (RFC 1952) from DEFLATE segments ----
+ * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec:
+ * BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
+ * a coded segment up to and including its end-of-block code, 8 * d_sizes[i] for a stored
+ * segment, BITAR_HIP_SEGMENT_ERROR for a failed one.  d_bits NULL: exactly
+ * bitar_hip_compress.  The encoders guarantee: a coded segment is ONE block with BFINAL at bit
+ * 0 of byte 0; a stored segment is ceil(n / 65535) byte-aligned stored blocks whose header
+ * bytes are 0 except the last one's, which is 1. */
+int bitar_hip_compress_bits(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const void* d_in,
+                            uint64_t n, uint32_t seg, void* d_slab, uint64_t slot_stride,
+                            uint32_t* d_sizes, uint32_t* d_bits);
+
+/* Join the nseg slots of such a call into ONE raw DEFLATE stream (RFC 1951) at d_joined:
+ * coded blocks are spliced at bit granularity with BFINAL cleared in all but the last, a
+ * stored segment keeps its byte alignment behind a 3-bit header.  d_starts (nseg+1) receives
+ * each segment's bit position and, last, the stream's bit length; the stream is
+ * ceil(d_starts[nseg] / 8) bytes with zero padding bits.  d_joined NULL: positions only.
+ * d_joined must be 4-B aligned and `capacity` a multiple of 4 (else BITAR_HIP_INVALID: the
+ * stream is written in whole dwords); it is zeroed over `capacity` bytes first.  The stream
+ * needs at most sum(d_sizes) + nseg bytes, so that rounded up to 4 always suffices.  Nothing
+ * past `capacity` is read or written; a stream that needs more
+ * (or a failed segment, which joins as nothing) makes the next bitar_hip_sync of `stream`
+ * return BITAR_HIP_IO_ERROR.  Asynchronous on `stream`: positions and lengths never visit the
+ * host. */
+int bitar_hip_deflate_join(bitar_hip_ctx* ctx, void* stream, const void* d_slab,
+                           uint64_t slot_stride, const uint32_t* d_sizes, const uint32_t* d_bits,
+                           uint32_t nseg, uint64_t* d_starts, void* d_joined, uint64_t capacity);
+
+/* The inverse, for parallel decode: slot i (d_slab + i*slot_stride, 16-B aligned) receives the
+ * segment at bit d_starts[i] of the joined stream (d_joined, 4-B aligned, joined_len bytes)
+ * as the encoder wrote it, BFINAL set again, and d_sizes[i] its size, ready for
+ * bitar_hip_decompress_slab.  d_entries[i] = bits | stored << 23 (bits = 8 * size for a stored
+ * segment).  d_starts and d_entries may come from an untrusted header: an entry that reaches
+ * past 8 * joined_len bits or whose size exceeds slot_stride gives d_sizes[i] =
+ * BITAR_HIP_SEGMENT_ERROR and BITAR_HIP_IO_ERROR at the next sync; nothing is read or written
+ * out of bounds. */
+int bitar_hip_deflate_split(bitar_hip_ctx* ctx, void* stream, const void* d_joined,
+                            uint64_t joined_len, const uint64_t* d_starts,
+                            const uint32_t* d_entries, uint32_t nseg, void* d_slab,
+                            uint64_t slot_stride, uint32_t* d_sizes);
+
+/* *d_crc = the CRC-32 of n bytes from the CRC-32s of their nseg = ceil(n / seg) segments
+ * (d_sums as bitar_hip_checksum writes them, CRC-32 in the low word): zlib's crc32_combine
+ * over all segments at once. */
+int bitar_hip_crc32_combine(bitar_hip_ctx* ctx, void* stream, const uint64_t* d_sums, uint64_t n,
+                            uint32_t seg, uint32_t nseg, uint32_t* d_crc);
+
 /* Decoder selection of one context.  The decoders are interchangeable (every one accepts and
  * rejects exactly what the oracle does); the options pick which kernels run, for tests and
  * tuning.  No reference counterpart: the BlueField engine has one decoder. */
