@@ -5,10 +5,17 @@
 // i*seg of the caller's buffer).  Acceptance rules are exactly those of the oracle's
 // bo_lz4_decompress_block (oracle/bitar_oracle.c), so malformed input fails identically:
 // the block format's end conditions (final literal run >= 5 bytes, last match >= 12 bytes
-// before the end) and liblz4's two limits on length-extension bytes included.  Batches
-// never meet those (they stop >= 132 stream bytes before the end), so the general path
+// before the end) and liblz4's two limits on length-extension bytes included.  The fast
+// paths never meet those (they stop >= 132 stream bytes before the end), so the general path
 // checks them, the last match's length coming from the general path or -- when the final
-// token directly follows a batch -- from a re-walk of that batch's headers.
+// token directly follows a fast-path sequence -- from the last record the near kernel's list
+// flushed, or from a re-walk of the far kernel's last batch's headers.
+//
+// Fast paths: the near kernel (lz4_decompress_kernel<false>, every segment) parses 64 stream
+// positions at a time, follows the token chain over the whole parsed window, appends the
+// chain's sequences to a list of <= 64 records held in registers and gathers the listed
+// sequences' output 64 bytes per step ("the list path", below); the far kernel (<true>, stock
+// streams with offsets past the LDS ring) keeps the 128-byte batches (`batch`).
 //
 // Per wave LDS (one wave per workgroup):
 //   win[kWin]   the compressed stream, staged from HBM 16 B per lane (dwordx4), refilled
@@ -24,8 +31,9 @@
 
 #include <type_traits>
 
-// diagnostic build: count batches, their bytes, general-path sequences and why walks end
-// (BITAR_HIP_PATH_LZ4_* 11..15; costs a few SALU per batch, so off by default)
+// diagnostic build: count batches (the near kernel: list flushes), their bytes, general-path
+// sequences and why walks end (BITAR_HIP_PATH_LZ4_* 11..15; costs a few SALU per batch /
+// window, so off by default)
 #ifndef BITAR_LZ4D_PROFILE
 #define BITAR_LZ4D_PROFILE 0
 #endif
@@ -216,17 +224,61 @@ __device__ __forceinline__ uint32_t walk_tokens2h(uint32_t pw, uint32_t lim, uin
   return out;
 }
 
+// ---- the near kernel's sequence list ----------------------------------------------------
+// One record per lane, in two registers: w0 = offset | literal count << 16 | output length
+// << 24, w1 = LDS address of the first literal (in the stream window).  A parsed window
+// appends its chain's records; a flush gathers the listed sequences' output 64 bytes a step.
+constexpr uint32_t kListCap = kWave;
+// sequences one window can append: chain lanes 0, 3, .., 60 (a sequence is >= 3 stream bytes
+// and lane 63 never qualifies)
+constexpr uint32_t kWinSeqs = (kWave - 1 + 2) / 3;
+// walk word: the next token's lane (<= 127 when this token is eligible) | 128 if that lane is
+// not an eligible token, so the walk goes on exactly while the word is < 64
+constexpr uint32_t kNextStop = 128;
+
+// The list path's token walk: from lane 0 (eligible: the caller's test), set every chain
+// lane in `chain`; one v_readlane (the word read is the next lane select), one s_bitset1,
+// one compare and one branch per sequence, unrolled twice.  A VALU-written SGPR needs 4
+// wait states before it is a lane select: s_nop 0, the compare, the branch and the bitset.
+// Returns the word that ended the walk (> 63).
+__device__ __forceinline__ uint32_t walk_chain(uint32_t nx, uint64_t& chain) {
+  uint32_t l = 0;
+  __asm__ volatile(
+      "L_wc_%=:\n"
+      "s_bitset1_b64 %[ch], %[l]\n"
+      "v_readlane_b32 %[l], %[nx], %[l]\n"
+      "s_nop 0\n"
+      "s_cmp_gt_u32 %[l], 63\n"
+      "s_cbranch_scc1 L_wo_%=\n"
+      "s_bitset1_b64 %[ch], %[l]\n"
+      "v_readlane_b32 %[l], %[nx], %[l]\n"
+      "s_nop 0\n"
+      "s_cmp_lt_u32 %[l], 64\n"
+      "s_cbranch_scc1 L_wc_%=\n"
+      "L_wo_%=:\n"
+      : [l] "+s"(l), [ch] "+s"(chain)
+      : [nx] "v"(nx)
+      : "scc");
+  return l;
+}
+// a on the lanes set in m, b on the others
+__device__ __forceinline__ uint32_t lane_sel(uint64_t m, uint32_t a, uint32_t b) {
+  uint32_t r;
+  __asm__("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+  return r;
+}
+
 }  // namespace lz4d
 
 // Two instantiations, launched back to back by the runtime:
-//   FARK = false  every segment; batches admit offsets within the ring only (our own streams
-//                 never go beyond it).  A segment whose next sequence could be batched only
-//                 with far history (stock streams: offsets up to 65535) is deferred
-//                 (produced = kDefer) as soon as that is seen.
-//   FARK = true   the deferred segments only (the others exit at once): FAR batches read far
-//                 history back from HBM, and stay FAR while they meet it.
-// Keeping the far machinery out of the first kernel keeps its batch path as short as before
-// (measured: 4-8 % on our own streams when both share one kernel).
+//   FARK = false  every segment, by the list path; the list admits offsets within the ring
+//                 only (our own streams never go beyond it).  A segment whose next sequence
+//                 could be listed only with far history (stock streams: offsets up to 65535)
+//                 is deferred (produced = kDefer) as soon as that is seen.
+//   FARK = true   the deferred segments only (the others exit at once), by 128-byte batches:
+//                 FAR batches read far history back from HBM, and stay FAR while they meet it.
+// Keeping the far machinery out of the first kernel keeps its fast path short (measured with
+// the batches: 4-8 % on our own streams when both share one kernel).
 constexpr uint32_t kDefer = 0xFFFFFFFEu;
 
 template <bool FARK>
@@ -266,7 +318,10 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
   const uint32_t src_lo = (uint32_t)(uintptr_t)s.src;
   bool want_far = false, stay_far = false;
   // end-of-block conditions: the last match's length (0 = it was in the batch at bip)
-  uint32_t last_ml = 0, bip = 0, fin_lit = 0, fin_tok = 0;
+  uint32_t last_ml = 0, fin_lit = 0, fin_tok = 0;
+  [[maybe_unused]] uint32_t bip = 0;
+  // the near kernel's pending sequences: lane j holds record j (lz4d: the list's words)
+  [[maybe_unused]] uint32_t nseq = 0, lw0 = 0, lw1 = 0;
   [[maybe_unused]] uint32_t p_batches = 0, p_bytes = 0, p_general = 0, p_stop_parse = 0,
                             p_stop_inel = 0;
   while (ok) {
@@ -440,30 +495,19 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
         ring[(base + s.op + q) & kRingMask] = (uint8_t)g;
         lds_order();
       };
-      auto half = [&](auto h_tag, uint32_t key) __attribute__((always_inline)) {
-        finish(h_tag, prep(h_tag, key));
-      };
       // every output byte takes the record of the latest sequence starting at or before it
       // (a written word has bit 31 clear, so its key is >= 0; the first sequence's, at lane
       // 0, is 0, so every half-0 key ends >= 0)
-#ifndef BITAR_LZ4D_KEYS2
-#define BITAR_LZ4D_KEYS2 1
-#endif
       const uint32_t key0 =
           (uint32_t)wave_incl_max_i((int32_t)((vrec0 & 0x8000003Fu) | (lane << 24)));
-#if BITAR_LZ4D_KEYS2
       // (both halves' scans side by side: each DPP step's two wait states filled by the
       // other scan's; the second is wasted on a batch of <= 64 bytes)
       const int32_t key1 =
           wave_incl_max_i((int32_t)((vrec1 & 0x8000003Fu) | ((lane + kWave) << 24)));
-#endif
-#ifndef BITAR_LZ4D_SPLIT
-#define BITAR_LZ4D_SPLIT 1
-#endif
-#if BITAR_LZ4D_KEYS2 && BITAR_LZ4D_SPLIT
       // both halves' sources worked out before either gathers (independent work side by
       // side; the second half's is wasted on a batch of <= 64 bytes), then half 0's gather and
-      // store, then half 1's, which may read half 0's bytes from the ring
+      // store, then half 1's, which may read half 0's bytes from the ring; the second half
+      // takes its own starts (all past byte 64), else the first half's last record
       {
         const uint32_t st0 = prep(std::integral_constant<uint32_t, 0>{}, key0);
         const int32_t carry = (int32_t)readlane(key0, kWave - 1);
@@ -472,22 +516,6 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
         finish(std::integral_constant<uint32_t, 0>{}, st0);
         if (out > kWave) finish(std::integral_constant<uint32_t, 1>{}, st1);
       }
-      if (false) {
-#else
-      half(std::integral_constant<uint32_t, 0>{}, key0);
-#endif
-      if (out > kWave) {
-        // second half: its own starts (all past byte 64), else the first half's last record
-#if !BITAR_LZ4D_KEYS2
-        const int32_t key1 =
-            wave_incl_max_i((int32_t)((vrec1 & 0x8000003Fu) | ((lane + kWave) << 24)));
-#endif
-        const int32_t carry = (int32_t)readlane(key0, kWave - 1);
-        half(std::integral_constant<uint32_t, 1>{}, (uint32_t)(key1 > carry ? key1 : carry));
-      }
-#if BITAR_LZ4D_KEYS2 && BITAR_LZ4D_SPLIT
-      }
-#endif
       if constexpr (BITAR_LZ4D_ENDRULES == 1 || BITAR_LZ4D_ENDRULES == 2) {
         bip = s.ip;
         last_ml = 0;
@@ -497,36 +525,253 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
       return out;
     };
     if constexpr (!FARK) {
-      // one loop condition computed at the end of each batch (the for / continue / break
-      // form compiles to ~12 SALU of uniform-bool bookkeeping per batch)
+      // ---- list fast path: parse -> walk -> list -> gather --------------------------------
+      // 1. the speculative parse of 64 stream positions, as in `batch` above;
+      // 2. the walk follows the real token chain over the WHOLE parsed window and only sets
+      //    the chain lanes in a scalar mask (no output room, no placement);
+      // 3. the chain lanes' records are appended to the list (index: v_mbcnt of the mask +
+      //    the pending count; moved with ds_permute, which needs no LDS memory);
+      // 4. the list is flushed when it could not take another window's sequences, and before
+      //    the stream window is refilled (records point into it), the general path runs or
+      //    the segment ends: one prefix sum places the sequences, the capacity is checked
+      //    once, then every step gathers 64 output bytes.
       want_far = false;
-      if (s.ip + kBatchIn <= s.csize) {
-        uint32_t t;
-        do {
-          const uint32_t o = batch(std::false_type{});
-          // "a batch was made and the next one fits the stream": one compare (the select
-          // in asm, so the compiler keeps it a single scalar branch)
-          const uint32_t rest = s.csize - s.ip;
-          __asm__("s_cmp_lg_u32 %1, 0\n s_cselect_b32 %0, %2, 0" : "=s"(t) : "s"(o), "s"(rest)
-                  : "scc");
-        } while (t >= kBatchIn);
+      for (;;) {
+        // after the flush: 1 = parse on (the list was full or the stream window at its end),
+        // 0 = the general path (an ineligible token, or the block's last kBatchIn bytes)
+        uint32_t more = 0;
+        if (s.ip + kBatchIn <= s.csize) {
+          uint32_t wrel = src_lo + s.ip - (uint32_t)s.wb;  // window index of ip (mod 2^32)
+          if (wrel > kWin - kBatchIn) {  // (the list is empty here: a flush came before)
+            win_at(s, win, s.ip, kBatchIn);
+            wrel = src_lo + s.ip - (uint32_t)s.wb;
+          }
+          uint32_t t;
+          do {
+            // (1) one candidate token per lane: token, optional literal length byte,
+            //     literals, offset, optional match length byte
+            lds_order();
+            const uint32_t wc = wrel + lane;
+            const uint32_t tok = win[wc];
+            const uint32_t b1 = win[wc + 1];
+            const uint32_t cm4 = tok & 15u;
+            const bool lx = (tok >> 4) == 15u, mx = cm4 == 15u;
+            const uint32_t cL = lx ? 15u + b1 : tok >> 4;
+            const uint32_t ob = wc + 1 + (lx ? 1u : 0u) + cL;  // offset position
+            const uint32_t cb0 = win[ob], cb1 = win[ob + 1], b2 = win[ob + 2];
+            const uint32_t coff = cb0 | (cb1 << 8);
+            const uint32_t cml = 4 + (mx ? 15u + b2 : cm4);
+            const uint32_t colen = cL + cml;
+            // eligible: as in `batch`, except that the token need not open the list: "not
+            // before the segment start" is tested against the output position at the last
+            // flush plus the token's own literals (its true position is at or past that, so
+            // this only sends more sequences down the general path near a segment's start)
+            const bool cfar = (colen <= kSeqOut) & (coff - 1u < s.op + cL);
+            const bool celig = cfar & (coff <= kNearOff) & (lane < kWave - 1);
+            const uint64_t E = ballot(celig);
+            if (!(E & 1ull)) {
+              // the first token is not eligible; if it would be with far history, defer the
+              // segment
+              want_far = (ballot(cfar) & 1ull) != 0;
+              more = 0;
+              break;
+            }
+            {
+              // walk word: "the next token is not eligible" folded into the next lane
+              const uint32_t nxt = lane + 3 + (lx ? 1u : 0u) + (mx ? 1u : 0u) + cL;
+              const uint32_t inel = (uint32_t)(~E >> (nxt & 63u)) & 1u;
+              const uint32_t nxw = nxt | (inel * kNextStop);
+              // (2) the chain's lanes
+              uint64_t chain = 0;
+              const uint32_t stop = walk_chain(nxw, chain);
+              const uint32_t adv = stop & (kNextStop - 1);
+              // (3) append: chain lane -> list lane nseq + its rank; the other lanes' words
+              //     go to a lane outside the appended range
+              const uint32_t cnt = (uint32_t)__builtin_popcountll(chain);
+              const uint32_t idx = __builtin_amdgcn_mbcnt_hi(
+                  (uint32_t)(chain >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)chain, nseq));
+              const uint32_t spare = (nseq + cnt) & (kListCap - 1);
+              const int to = (int)(lane_sel(chain, idx, spare) << 2);
+              const uint32_t w0 = coff | (cL << 16) | (colen << 24);
+              const uint32_t w1 = kRing + wc + 1u + (lx ? 1u : 0u);
+              uint32_t n0 = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)w0);
+              uint32_t n1 = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)w1);
+              __asm__("" : "+v"(n0), "+v"(n1));
+              const bool fresh = lane - nseq < cnt;
+              lw0 = fresh ? n0 : lw0;
+              lw1 = fresh ? n1 : lw1;
+              nseq += cnt;
+              s.ip += adv;
+              wrel += adv;
+              more = 1;
+              if constexpr (BITAR_LZ4D_PROFILE != 0) {
+                if (adv >= kWave - 1) p_stop_parse += 1;
+                else p_stop_inel += 1;
+              }
+              // one loop condition: the list takes another window's sequences, the next
+              // window is staged, and the stream has kBatchIn bytes left (the selects in asm,
+              // so the compiler keeps it a single scalar branch)
+              const uint32_t rest = s.csize - s.ip;
+              __asm__("s_cmp_le_u32 %1, %3\n s_cselect_b32 %0, %2, 0\n"
+                      "s_cmp_le_u32 %4, %5\n s_cselect_b32 %0, %0, 0"
+                      : "=&s"(t)
+                      : "s"(nseq), "s"(rest), "i"(kListCap - kWinSeqs), "s"(wrel),
+                        "i"(kWin - kBatchIn)
+                      : "scc");
+              // a walk ended by an ineligible token: flush first, so that the token is parsed
+              // again against the output position it really has (the deferral test is then
+              // exact, as it was when every batch began at the output position)
+              if (adv < kWave - 1) t = 0;
+            }
+          } while (t >= kBatchIn);
+        }
+        if (want_far) break;
+        if (nseq) {
+          // (4) flush.  Positions are relative to the output position at the flush (q: this
+          // lane's byte, R: the step's first); per record: os = its first byte, rM = its
+          // match's first byte, rD = its literals' LDS address less q.
+          const bool live = lane < nseq;
+          const uint32_t len = live ? lw0 >> 24 : 0u;
+          const uint32_t incl = wave_incl_sum(len);
+          const uint32_t total = readlane(incl, kWave - 1);
+          if (total > s.cap - s.op) { ok = false; break; }  // (op <= cap always)
+          if constexpr (BITAR_LZ4D_ENDRULES == 1 || BITAR_LZ4D_ENDRULES == 2) {
+            const uint32_t lastw = readlane(lw0, nseq - 1);  // the last match's length
+            last_ml = (lastw >> 24) - ((lastw >> 16) & 0xFFu);
+          }
+          if constexpr (BITAR_LZ4D_PROFILE != 0) {
+            p_batches += 1;
+            p_bytes += total;
+          }
+          const uint32_t os = incl - len;
+          const uint32_t rM = os + ((lw0 >> 16) & 0xFFu);
+          const uint32_t rD = lw1 - os;
+          // 4 * (os - R - 1): the lane this record marks in the step that holds its first
+          // byte; lanes past the list never come into a step
+          uint32_t d4 = live ? (os << 2) - 4u : 0x40000000u;
+          uint32_t one = 1u;
+          __asm__("" : "+v"(one));
+          const uint32_t rb0 = base + s.op;  // ring index of byte q = (rb0 + q) & mask
+          uint32_t q = lane;
+          // One round of N steps of 64 bytes from byte R on: the steps' sources are worked out
+          // side by side (their LDS round trips overlap), then step 0's pointer doubling,
+          // gather and store, then step 1's, which may read step 0's bytes from the ring.  A
+          // flush's last odd step is a round of one.
+          auto round = [&](auto n_tag, uint32_t R) __attribute__((always_inline)) {
+            constexpr uint32_t kSteps = decltype(n_tag)::value;
+            // whose byte: every record starting in the step marks the lane below its first
+            // byte's (ds_permute; a lane nobody writes reads 0).  Records starting before or after
+            // the step, or at the step's first byte, all write lane 63, whose mark is not used;
+            // a record starting at lane t >= 1 marks lane t - 1, so the byte's record is
+            // (records starting at or before the step's first byte) - 1 + (marks in lanes
+            // below t): one v_mbcnt pair, no shift of the mask.
+            uint32_t rec[kSteps], ms[kSteps], dl[kSteps], st[kSteps];
+            int32_t srel[kSteps];
+#pragma unroll
+            for (uint32_t j = 0; j < kSteps; ++j) {
+              const uint32_t dj = d4 - j * 4u * kWave;
+              const uint32_t mk = (uint32_t)__builtin_amdgcn_ds_permute(
+                  (int)(dj < 4u * (kWave - 1) ? dj : 4u * (kWave - 1)), (int)one);
+              const uint64_t S1 = ballot(mk != 0u);  // (lane 63's bit is never counted)
+              const uint32_t cov4 =
+                  ((uint32_t)__builtin_popcountll(ballot((int32_t)dj < 0)) - 1u) << 2;
+              const uint32_t idx = __builtin_amdgcn_mbcnt_hi(
+                  (uint32_t)(S1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)S1, 0u));
+              const int from = (int)((idx << 2) + cov4);
+              rec[j] = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)lw0);
+              ms[j] = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)rM);
+              dl[j] = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)rD);
+              const uint32_t qj = q + j * kWave;
+              // q - off (SDWA takes the offset's 16 bits in place)
+              __asm__("v_sub_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD "
+                      "src0_sel:DWORD src1_sel:WORD_0"
+                      : "=v"(srel[j]) : "v"(qj), "v"(rec[j]));
+            }
+            // overlapping copy (source inside the match itself): fold the source into the
+            // first period, as in `batch`; skipped when no byte of the round needs it
+            uint64_t lap = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < kSteps; ++j) lap |= ballot(srel[j] >= (int32_t)ms[j]);
+            if (lap) {
+#pragma unroll
+              for (uint32_t j = 0; j < kSteps; ++j) {
+                const uint32_t joff = rec[j] & 0xFFFFu;
+                const uint32_t m = (q + j * kWave - ms[j]) & 63u;
+                const float qf = floorf(((float)m + 0.5f) *
+                                        __builtin_amdgcn_rcpf((float)(joff > 1u ? joff : 1u)));
+                int32_t sf = (int32_t)(ms[j] + m - (uint32_t)qf * joff) - (int32_t)joff;
+                __asm__("" : "+v"(sf));  // (pinned: a select, no exec-mask branch)
+                srel[j] = srel[j] >= (int32_t)ms[j] ? sf : srel[j];
+              }
+            }
+            // which byte: a window literal, ring history (bytes before the step are in the
+            // ring once the step gathers), or an earlier byte of this step (an alias: bit 31 |
+            // its lane, q - off mod 64 as the step's first byte is a multiple of 64)
+#pragma unroll
+            for (uint32_t j = 0; j < kSteps; ++j) {
+              const uint32_t qj = q + j * kWave;
+              uint32_t lit_a = dl[j] + qj, hist_a = (rb0 + (uint32_t)srel[j]) & kRingMask,
+                       alias_a = (uint32_t)srel[j] | 0x80000000u;
+              __asm__("" : "+v"(lit_a), "+v"(hist_a), "+v"(alias_a));
+              const uint32_t sj = srel[j] >= (int32_t)(R + j * kWave) ? alias_a : hist_a;
+              st[j] = qj < ms[j] ? lit_a : sj;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < kSteps; ++j) {
+              // pointer doubling: every alias chain strictly descends (its source lane is
+              // below its own, past-the-end bytes included), so <= 6 rounds; the count is
+              // only a guard
+              uint32_t a, o, n, sj = st[j];
+              __asm__ volatile(
+                  "s_mov_b32 %[n], 7\n"
+                  "L_ld_%=:\n"
+                  "v_cmp_gt_i32_e32 vcc, 0, %[st]\n"
+                  "s_cbranch_vccz L_le_%=\n"
+                  "s_sub_u32 %[n], %[n], 1\n"
+                  "s_cbranch_scc1 L_le_%=\n"
+                  "v_lshlrev_b32_e32 %[a], 2, %[st]\n"
+                  "ds_bpermute_b32 %[o], %[a], %[st]\n"
+                  "s_waitcnt lgkmcnt(0)\n"
+                  "v_cndmask_b32_e32 %[st], %[st], %[o], vcc\n"
+                  "s_branch L_ld_%=\n"
+                  "L_le_%=:\n"
+                  : [st] "+v"(sj), [a] "=&v"(a), [o] "=&v"(o), [n] "=&s"(n)
+                  :
+                  : "vcc", "scc", "memory");
+              // one gather, one store; all 64 bytes are stored: those past the flush's end
+              // land in ring slots > kNearOff behind the output, already flushed and
+              // rewritten before use
+              lds_order();
+              const uint32_t g = lds[sj];
+              ring[(rb0 + q + j * kWave) & kRingMask] = (uint8_t)g;
+              lds_order();
+            }
+          };
+          for (uint32_t R = 0; R < total; R += 2 * kWave) {
+            if (s.op + 2 * kWave - s.flushed > kFlushAt) flush(s, ring, s.op, false);
+            const uint32_t left = total - R;
+            if (left > kWave) round(std::integral_constant<uint32_t, 2>{}, R);
+            else round(std::integral_constant<uint32_t, 1>{}, R);
+            s.op += left < 2 * kWave ? left : 2 * kWave;
+            d4 -= 2 * 4u * kWave;
+            q += 2 * kWave;
+          }
+          nseq = 0;
+        }
+        if (!more) break;
       }
+      if (!ok) break;
     } else
     for (;;) {
+      // (the far kernel only: near batches while they do, FAR ones where they meet far history)
       if (s.ip + kBatchIn > s.csize) break;
-      if constexpr (FARK) {
-        if (stay_far) {
-          if (batch(std::true_type{})) continue;
-          stay_far = false;
-        }
-        want_far = false;
-        if (batch(std::false_type{})) continue;
-        if (!want_far || !batch(std::true_type{})) break;
-      } else {
-        want_far = false;
-        if (batch(std::false_type{})) continue;
-        break;
+      if (stay_far) {
+        if (batch(std::true_type{})) continue;
+        stay_far = false;
       }
+      want_far = false;
+      if (batch(std::false_type{})) continue;
+      if (!want_far || !batch(std::true_type{})) break;
     }
     if (!FARK && want_far) break;  // defer the segment to the FAR kernel
     // ---- general path: one sequence, any shape -----------------------------------------
@@ -576,7 +821,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
   if ((BITAR_LZ4D_ENDRULES == 1 || BITAR_LZ4D_ENDRULES == 3) && ok && s.op > fin_lit &&
       !(!FARK && want_far)) {
     uint32_t ml = last_ml;
-    if (ml == 0 && fin_lit >= 5 && fin_lit < 8) {
+    if (FARK && ml == 0 && fin_lit >= 5 && fin_lit < 8) {
       for (uint32_t p = bip; p < fin_tok;) {
         const uint32_t t = sv.get(s, win, p);
         uint32_t ll = t >> 4, mm = t & 15u;

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""LZ4 decoder batch diagnostics: run with a -DBITAR_LZ4D_PROFILE=1 library
+"""LZ4 decoder list-path diagnostics: run with a -DBITAR_LZ4D_PROFILE=1 library
    (scripts/build_variant.sh prof "-DBITAR_LZ4D_PROFILE=1"; BITAR_HIP_LIB=...) and print, per
-   input kind, batches per segment, output bytes per batch, the share of output the batches
-   produced, general-path sequences and why walks ended."""
+   input kind, list flushes per segment (the counters' "batches"), output bytes per flush, the
+   share of output the list path produced, general-path sequences, parsed windows per flush
+   and the share of walks ended by the parsed window's end / by an ineligible token."""
 import json
 import os
 import sys
@@ -30,12 +31,14 @@ def main():
         c = eng.path_counters()
         assert torch.equal(out, data)
         b = max(c["lz4_batches"], 1)
-        print(json.dumps({"kind": kind, "batches_per_seg": round(c["lz4_batches"] / nseg, 1),
-                          "bytes_per_batch": round(c["lz4_batch_bytes"] / b, 1),
-                          "batch_share": round(c["lz4_batch_bytes"] / n, 3),
+        w = max(c["lz4_stop_parse"] + c["lz4_stop_ineligible"], 1)  # one walk per window
+        print(json.dumps({"kind": kind, "flushes_per_seg": round(c["lz4_batches"] / nseg, 1),
+                          "bytes_per_flush": round(c["lz4_batch_bytes"] / b, 1),
+                          "list_share": round(c["lz4_batch_bytes"] / n, 3),
                           "general_seqs_per_seg": round(c["lz4_general_seqs"] / nseg, 1),
-                          "stop_parse": round(c["lz4_stop_parse"] / b, 3),
-                          "stop_ineligible": round(c["lz4_stop_ineligible"] / b, 3)}))
+                          "windows_per_flush": round(w / b, 2),
+                          "stop_parse": round(c["lz4_stop_parse"] / w, 3),
+                          "stop_ineligible": round(c["lz4_stop_ineligible"] / w, 3)}))
     eng.close()
 
 
