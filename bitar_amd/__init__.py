@@ -20,6 +20,7 @@ CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
+FILTER_SHUFFLE, FILTER_BITSHUFFLE = 1, 2  # bitar_hip_filter (element widths 2, 4, 8, 16)
 # bitar_hip_config.flags (initial decoder options of a context)
 FLAG_INFLATE_WAVE_ONLY, FLAG_ZSTD_WAVE_ONLY, FLAG_ZSTD_LANE_EXEC, FLAG_COUNT_PATHS = 1, 2, 4, 8
 FLAG_PLAIN_ORDER = 0x10  # segment i is workgroup i (no cost-ordered dispatch; same output)
@@ -104,6 +105,8 @@ def lib():
         "bitar_hip_deflate_join": (i32, [vp, vp, vp, u64, vp, vp, u32, vp, vp, u64]),
         "bitar_hip_deflate_split": (i32, [vp, vp, vp, u64, vp, vp, u32, vp, u64, vp]),
         "bitar_hip_crc32_combine": (i32, [vp, vp, vp, u64, u32, u32, vp]),
+        "bitar_hip_filter_apply": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
+        "bitar_hip_filter_invert": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -126,7 +129,7 @@ ABI_SYMBOLS = ("bitar_hip_abi_version", "bitar_hip_last_error", "bitar_hip_devic
                "bitar_hip_set_decoder_options", "bitar_hip_path_counters",
                "bitar_hip_compress_host", "bitar_hip_decompress_host",
                "bitar_hip_compress_bits", "bitar_hip_deflate_join", "bitar_hip_deflate_split",
-               "bitar_hip_crc32_combine")
+               "bitar_hip_crc32_combine", "bitar_hip_filter_apply", "bitar_hip_filter_invert")
 
 
 def check(rc):
@@ -277,6 +280,26 @@ class Engine:
         nseg = (n + seg - 1) // seg if nseg is None else nseg
         check(lib().bitar_hip_checksum(self.ctx, self._stream(stream), kind, _ptr(data), n, seg,
                                        _ptr(lens), nseg, _ptr(sums)))
+
+    # --- shuffle / bitshuffle of fixed-width column buffers, per segment ------------------
+    def _filter(self, fn, filter, width, data, seg, out, n, lens, nseg, stream):
+        n = data.numel() * data.element_size() if n is None else n
+        nseg = (n + seg - 1) // seg if nseg is None and seg > 0 else nseg or 0
+        check(fn(self.ctx, self._stream(stream), filter, width, _ptr(data), n, seg, _ptr(lens),
+                 nseg, _ptr(out)))
+
+    def filter_into(self, filter, width, data, seg, out, n=None, lens=None, nseg=None,
+                    stream=None):
+        """segment i of `data` (lens[i] bytes, or min(seg, n - i*seg)) filtered into `out` at
+        the same offset: FILTER_SHUFFLE or FILTER_BITSHUFFLE of `width`-byte elements"""
+        self._filter(lib().bitar_hip_filter_apply, filter, width, data, seg, out, n, lens, nseg,
+                     stream)
+
+    def unfilter_into(self, filter, width, data, seg, out, n=None, lens=None, nseg=None,
+                      stream=None):
+        """the inverse of filter_into (lens: e.g. the produced sizes of a decompress)"""
+        self._filter(lib().bitar_hip_filter_invert, filter, width, data, seg, out, n, lens, nseg,
+                     stream)
 
     # --- one DEFLATE stream from the segments' streams (gzip members) -------------------
     def compress_bits_into(self, codec, data, seg, slab, stride, sizes, bits, n=None,

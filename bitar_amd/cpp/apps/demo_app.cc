@@ -2,6 +2,7 @@
 //
 //   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd]
 //            [--seg N] [--devices N] [--workers N] [--ipc-codec none|zstd|lz4]
+//            [--filter shuffle|bitshuffle --element-width 2|4|8|16]
 //   demo_app --synthetic N ...      (no file: N bytes of a generated mixed buffer)
 //
 // ReadData (demo_app.cc:295-330):
@@ -282,10 +283,10 @@ arrow::Status EvaluateAsync(const std::vector<std::unique_ptr<Device>>& devs,
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string file, codec_name = "deflate", ipc_codec = "none";
+  std::string file, codec_name = "deflate", ipc_codec = "none", filter_name = "none";
   int64_t bytes = 0, synthetic = 0;
   int mode = 0;
-  uint32_t seg = 59460, ndev = 1, workers = 4;
+  uint32_t seg = 59460, ndev = 1, workers = 4, element_width = 1;
   for (int i = 1; i + 1 < argc; i += 2) {
     const std::string a = argv[i], v = argv[i + 1];
     if (a == "--file" || a == "-f") file = v;
@@ -297,6 +298,8 @@ int main(int argc, char** argv) {
     else if (a == "--devices") ndev = static_cast<uint32_t>(std::stoul(v));
     else if (a == "--workers") workers = static_cast<uint32_t>(std::stoul(v));
     else if (a == "--ipc-codec") ipc_codec = v;
+    else if (a == "--filter") filter_name = v;
+    else if (a == "--element-width") element_width = static_cast<uint32_t>(std::stoul(v));
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
   }
   std::shared_ptr<arrow::Buffer> host;
@@ -313,6 +316,14 @@ int main(int argc, char** argv) {
   const auto codec = codec_name == "lz4"    ? bitar::Codec::LZ4
                      : codec_name == "zstd" ? bitar::Codec::ZSTD
                                             : bitar::Codec::DEFLATE;
+  // a per-segment transposition of --element-width byte values in front of the codec
+  if (filter_name != "none" && filter_name != "shuffle" && filter_name != "bitshuffle") {
+    std::cerr << "unknown filter " << filter_name << "\n";
+    return 2;
+  }
+  const auto filter = filter_name == "shuffle"      ? bitar::Filter::SHUFFLE
+                      : filter_name == "bitshuffle" ? bitar::Filter::BITSHUFFLE
+                                                    : bitar::Filter::NONE;
   auto* driver = bitar::CompressDriver<bitar::Class_HIP_GFX950>::Instance();
   auto ids = driver->ListAvailableDeviceIds();
   if (!ids.ok()) { std::cerr << ids.status().ToString() << "\n"; return 1; }
@@ -324,6 +335,8 @@ int main(int argc, char** argv) {
     auto cfg = std::make_unique<bitar::HipConfiguration>(bitar::HipConfiguration::Defaults());
     cfg->set_codec(codec);
     cfg->set_decompressed_seg_size32(seg);
+    if (filter != bitar::Filter::NONE)
+      cfg->set_filter(filter, static_cast<uint8_t>(std::min<uint32_t>(element_width, 255)));
     cfg->set_max_preallocate_memzones(static_cast<uint16_t>(
         std::min<int64_t>(65535, host->size() / seg + 64)));
     auto st = d->Initialize(std::move(cfg));

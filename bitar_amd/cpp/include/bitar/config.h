@@ -47,7 +47,14 @@ enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 
 /// rte_comp_checksum_type
 enum class ChecksumType : std::uint8_t { NONE = 0, CRC32 = 1, ADLER32 = 2, CRC32_ADLER32 = 3 };
 
+/// A per-segment transposition of fixed-width elements in front of the codec (no reference
+/// counterpart; include/bitar_hip.h bitar_hip_filter): SHUFFLE gathers byte j of every element
+/// (Blosc shuffle / Parquet BYTE_STREAM_SPLIT per segment), BITSHUFFLE bit b of byte j (the
+/// HDF5 bitshuffle layout).
+enum class Filter : std::uint8_t { NONE = 0, SHUFFLE = 1, BITSHUFFLE = 2 };
+
 std::string_view ToString(Codec c);
+std::string_view ToString(Filter f);
 std::string_view ToString(HuffmanEncoding h);
 std::string_view ToString(ChecksumType c);
 
@@ -156,10 +163,24 @@ class HipConfiguration : public Configuration<Class_HIP_GFX950> {
   [[nodiscard]] auto checksum_type() const noexcept { return checksum_type_; }
   void set_checksum_type(ChecksumType checksum_type) { checksum_type_ = checksum_type; }
 
+  /// Filter applied to every segment before it is compressed and undone after it is
+  /// decompressed; element_width is the column's value size in bytes, 2, 4, 8 or 16.  Checksums
+  /// stay over the caller's (unfiltered) bytes.  Both sides of a frame must be configured alike:
+  /// filter and width travel with the frame like codec and segment size.  Not combined with
+  /// chained ops (max_sgl_segs > 1).  Default: NONE, width 1.
+  [[nodiscard]] auto filter() const noexcept { return filter_; }
+  [[nodiscard]] auto element_width() const noexcept { return element_width_; }
+  void set_filter(Filter filter, std::uint8_t element_width) {
+    filter_ = filter;
+    element_width_ = element_width;
+  }
+
   static HipConfiguration Defaults() { return {}; }
 
  private:
   ChecksumType checksum_type_ = ChecksumType::NONE;
+  Filter filter_ = Filter::NONE;
+  std::uint8_t element_width_ = 1;
 };
 
 }  // namespace bitar

@@ -112,6 +112,12 @@ class CompressDevice {
   /// The checksum to compute per segment (BITAR_HIP_CHECKSUM_*), 0 for none.
   [[nodiscard]] virtual std::uint32_t checksum_kind() const { return 0; }
 
+  /// The filter of every segment (BITAR_HIP_FILTER_*, 0 for none) and its element width.
+  virtual void filter_kind(std::uint32_t* filter, std::uint32_t* width) const {
+    *filter = 0;
+    *width = 0;
+  }
+
   [[nodiscard]] auto state() const noexcept { return state_; }
   void set_state(internal::DeviceState state) { state_ = state; }
 
@@ -170,6 +176,7 @@ class HipCompressDevice : public HipGfx950CompressDevice {
   arrow::Status set_configuration(
       std::unique_ptr<Configuration<Class_HIP_GFX950>> configuration) override;
   [[nodiscard]] std::uint32_t checksum_kind() const override;
+  void filter_kind(std::uint32_t* filter, std::uint32_t* width) const override;
 
   friend arrow::Result<HipGfx950CompressDevice*>
   DeviceManager::Create<Class_HIP_GFX950>(std::uint8_t, std::vector<std::uint32_t>);

@@ -33,6 +33,15 @@ std::string_view ToString(ChecksumType c) {
   return "UNKNOWN";
 }
 
+std::string_view ToString(Filter f) {
+  switch (f) {
+    case Filter::NONE: return "NONE";
+    case Filter::SHUFFLE: return "SHUFFLE";
+    case Filter::BITSHUFFLE: return "BITSHUFFLE";
+  }
+  return "UNKNOWN";
+}
+
 template <typename Class, typename Enable>
 std::string Configuration<Class, Enable>::ToString() const {
   std::ostringstream os;
@@ -49,7 +58,9 @@ template class Configuration<Class_HIP_GFX950>;
 
 std::string HipConfiguration::ToString() const {
   return "{ " + Configuration<Class_HIP_GFX950>::ToString() +
-         ", checksum_type: " + std::string(bitar::ToString(checksum_type_)) + " }";
+         ", checksum_type: " + std::string(bitar::ToString(checksum_type_)) +
+         ", filter: " + std::string(bitar::ToString(filter_)) + "/" +
+         std::to_string(static_cast<int>(element_width_)) + " }";
 }
 
 }  // namespace bitar

@@ -156,6 +156,8 @@ struct QueuePairMemory {
   std::size_t table_cap = 0;
   void* d_stage = nullptr;
   std::uint64_t stage_cap = 0;
+  void* d_plain = nullptr;  // filter mode: the caller's (unfiltered) bytes of a host buffer
+  std::uint64_t plain_cap = 0;
   std::uint64_t* d_sums = nullptr;  // per-segment checksums (device, then pinned host)
   std::uint64_t* h_sums = nullptr;
   std::size_t sums_cap = 0;
@@ -185,6 +187,7 @@ struct QueuePairMemory {
     if (d_sizes) (void)bitar_hip_free(ctx, d_sizes);
     if (d_prod) (void)bitar_hip_free(ctx, d_prod);
     if (d_stage) (void)bitar_hip_free(ctx, d_stage);
+    if (d_plain) (void)bitar_hip_free(ctx, d_plain);
     if (d_sums) (void)bitar_hip_free(ctx, d_sums);
     if (h_sums) (void)bitar_hip_host_free(ctx, h_sums);
     if (d_chain) (void)bitar_hip_free(ctx, d_chain);
@@ -254,6 +257,16 @@ struct QueuePairMemory {
     stage_cap = 0;
     BITAR_ABI(bitar_hip_alloc(ctx, bytes, &d_stage), "qp staging");
     stage_cap = bytes;
+    return arrow::Status::OK();
+  }
+
+  arrow::Status Plain(std::uint64_t bytes) {
+    if (bytes <= plain_cap) return arrow::Status::OK();
+    if (d_plain) (void)bitar_hip_free(ctx, d_plain);
+    d_plain = nullptr;
+    plain_cap = 0;
+    BITAR_ABI(bitar_hip_alloc(ctx, bytes, &d_plain), "qp filter staging");
+    plain_cap = bytes;
     return arrow::Status::OK();
   }
 };
@@ -393,6 +406,18 @@ arrow::Result<BufferVector> CompressDevice<Class, Enable>::Compress(
     ARROW_RETURN_NOT_OK(m->Stage(n));
     d_in = m->d_stage;
   }
+  // filter mode (validated: max_sgl_segs == 1): the caller's bytes -- copied into d_plain
+  // whole when they are host memory, without the chunked overlap -- are filtered into d_stage
+  // and compressed from there; the checksums stay over the caller's bytes
+  std::uint32_t filter = 0, width = 0;
+  filter_kind(&filter, &width);
+  const void* d_plain = d_in;
+  if (filter) {
+    ARROW_RETURN_NOT_OK(m->Stage(n));
+    if (host_in) ARROW_RETURN_NOT_OK(m->Plain(n));
+    d_plain = host_in ? m->d_plain : h_in;
+    d_in = m->d_stage;
+  }
 
   std::vector<std::uint8_t*> slots;
   ARROW_RETURN_NOT_OK(device_memory_->Take(nseg, &slots));
@@ -423,7 +448,15 @@ arrow::Result<BufferVector> CompressDevice<Class, Enable>::Compress(
       m->h_ptrs[i] = static_cast<std::uint64_t>(reinterpret_cast<uintptr_t>(slots[i]));
     rc = m->UploadPtrs(nseg);
     const auto* dsts = reinterpret_cast<void* const*>(m->d_ptrs);
-    if (rc == 0 && host_in)
+    if (rc == 0 && filter) {
+      if (host_in) rc = bitar_hip_memcpy(ctx_, m->d_plain, h_in, n, m->stream);
+      if (rc == 0)
+        rc = bitar_hip_filter_apply(ctx_, m->stream, filter, width, d_plain, n, seg, nullptr, nseg,
+                                    m->d_stage);
+      if (rc == 0)
+        rc = bitar_hip_compress_scattered(ctx_, m->stream, codec, d_in, n, seg, dsts, slot_size_,
+                                          m->d_sizes);
+    } else if (rc == 0 && host_in)
       rc = bitar_hip_compress_host(ctx_, m->stream, codec, h_in, n, seg, m->d_stage, nullptr,
                                    dsts, slot_size_, m->d_sizes);
     else if (rc == 0)
@@ -448,7 +481,7 @@ arrow::Result<BufferVector> CompressDevice<Class, Enable>::Compress(
   if (rc == 0 && ck) {
     st = m->Sums(nops);
     if (!st.ok()) return release(st);
-    rc = bitar_hip_checksum(ctx_, m->stream, ck, d_in, n, static_cast<std::uint32_t>(opseg),
+    rc = bitar_hip_checksum(ctx_, m->stream, ck, d_plain, n, static_cast<std::uint32_t>(opseg),
                             nullptr, nops, m->d_sums);
     if (rc == 0) rc = bitar_hip_memcpy(ctx_, m->h_sums, m->d_sums, 8ull * nops, m->stream);
   }
@@ -547,7 +580,15 @@ arrow::Status CompressDevice<Class, Enable>::Decompress(
   }
   const auto out_addr = decompressed_buffer->mutable_address();
   const bool out_on_dev = internal::OnDevice(out_addr, device_id_);
-  const std::uint64_t out_bytes = out_on_dev ? 0 : static_cast<std::uint64_t>(min_capacity);
+  // filter mode (validated: max_sgl_segs == 1): the segments decode into staging and are
+  // inverted from there into the destination -- HBM directly, or d_plain and one copy for
+  // host output (no chunked overlap); the checksums are over the inverted bytes
+  std::uint32_t filter = 0, width = 0;
+  filter_kind(&filter, &width);
+  const bool decode_in_place = out_on_dev && !filter;
+  const std::uint64_t out_bytes = decode_in_place ? 0 : static_cast<std::uint64_t>(min_capacity);
+  if (filter && !out_on_dev)
+    ARROW_RETURN_NOT_OK(m->Plain(static_cast<std::uint64_t>(min_capacity)));
   if (host_bytes + out_bytes) ARROW_RETURN_NOT_OK(m->Stage(host_bytes + out_bytes));
   auto* stage = static_cast<std::uint8_t*>(m->d_stage);
   std::uint64_t off = out_bytes;
@@ -588,7 +629,8 @@ arrow::Status CompressDevice<Class, Enable>::Decompress(
                                    m->d_sizes + nseg, ngather),
               "gather compressed input");
   }
-  void* d_out = out_on_dev ? reinterpret_cast<void*>(out_addr) : m->d_stage;
+  void* d_out = decode_in_place ? reinterpret_cast<void*>(out_addr) : m->d_stage;
+  void* d_final = d_out;  // where the caller's bytes are on the device
   int rc = 0;
   std::uint32_t nunits = nseg;  // ops, one produced size / checksum each
   std::uint64_t unit = seg;
@@ -597,7 +639,15 @@ arrow::Status CompressDevice<Class, Enable>::Decompress(
     BITAR_ABI(m->UploadPtrs(nseg), "tables");
     BITAR_ABI(bitar_hip_memcpy(ctx_, m->d_sizes, m->h_sizes, 4ull * nseg, m->stream), "tables");
     const auto* srcs = reinterpret_cast<const void* const*>(m->d_ptrs);
-    if (!out_on_dev) {  // host output: decode chunks, each copied out while the next decodes
+    if (filter) {
+      d_final = out_on_dev ? reinterpret_cast<void*>(out_addr) : m->d_plain;
+      rc = bitar_hip_decompress(ctx_, m->stream, codec, srcs, m->d_sizes, nseg, seg, d_out,
+                                static_cast<std::uint64_t>(min_capacity), m->d_prod);
+      if (rc == 0)
+        rc = bitar_hip_filter_invert(ctx_, m->stream, filter, width, d_out,
+                                     static_cast<std::uint64_t>(min_capacity), seg, m->d_prod, nseg,
+                                     d_final);
+    } else if (!out_on_dev) {  // host output: decode chunks, each copied out while the next decodes
       rc = bitar_hip_decompress_host(ctx_, m->stream, codec, srcs, m->d_sizes, nseg, seg, d_out,
                                      reinterpret_cast<void*>(out_addr),
                                      static_cast<std::uint64_t>(min_capacity), m->d_prod);
@@ -653,12 +703,12 @@ arrow::Status CompressDevice<Class, Enable>::Decompress(
   const std::uint32_t ck = checksum_kind();
   if (rc == 0 && ck) {
     ARROW_RETURN_NOT_OK(m->Sums(nunits));
-    rc = bitar_hip_checksum(ctx_, m->stream, ck, d_out, static_cast<std::uint64_t>(min_capacity),
+    rc = bitar_hip_checksum(ctx_, m->stream, ck, d_final, static_cast<std::uint64_t>(min_capacity),
                             static_cast<std::uint32_t>(unit), m->d_prod, nunits, m->d_sums);
     if (rc == 0) rc = bitar_hip_memcpy(ctx_, m->h_sums, m->d_sums, 8ull * nunits, m->stream);
   }
   if (rc == 0 && !out_on_dev && !out_copied)
-    rc = bitar_hip_memcpy(ctx_, reinterpret_cast<void*>(out_addr), d_out,
+    rc = bitar_hip_memcpy(ctx_, reinterpret_cast<void*>(out_addr), d_final,
                           static_cast<std::uint64_t>(min_capacity), m->stream);
   if (rc == 0) rc = bitar_hip_sync(ctx_, m->stream);
   if (rc == 0) m->checksums.assign(m->h_sums, ck ? m->h_sums + nunits : m->h_sums);
@@ -787,7 +837,28 @@ arrow::Status HipCompressDevice::ValidateConfiguration() {
   if (ARROW_PREDICT_FALSE(hip_configuration == nullptr))
     return arrow::Status::Invalid("Invalid configuration for HipCompressDevice");
   // every rte_comp_checksum_type is supported (checksum.hip); see checksums()
+  if (hip_configuration->filter() != Filter::NONE) {
+    const auto w = hip_configuration->element_width();
+    if (hip_configuration->filter() != Filter::SHUFFLE &&
+        hip_configuration->filter() != Filter::BITSHUFFLE)
+      return arrow::Status::Invalid("Unknown filter");
+    if (w != 2 && w != 4 && w != 8 && w != 16)
+      return arrow::Status::Invalid("element_width (", +w,
+                                    ") of a filter must be 2, 4, 8 or 16");
+    if (hip_configuration->max_sgl_segs() > 1)
+      return arrow::Status::Invalid("A filter cannot be combined with chained operations "
+                                    "(max_sgl_segs > 1)");
+  }
   return HipGfx950CompressDevice::ValidateConfiguration();
+}
+
+void HipCompressDevice::filter_kind(std::uint32_t* filter, std::uint32_t* width) const {
+  const auto* c = dynamic_cast<const HipConfiguration*>(configuration().get());
+  *filter = 0;
+  *width = 0;
+  if (!c || c->filter() == Filter::NONE) return;
+  *filter = c->filter() == Filter::SHUFFLE ? BITAR_HIP_FILTER_SHUFFLE : BITAR_HIP_FILTER_BITSHUFFLE;
+  *width = c->element_width();
 }
 
 std::uint32_t HipCompressDevice::checksum_kind() const {

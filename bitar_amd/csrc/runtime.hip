@@ -92,6 +92,9 @@ __global__ void deflate_split_kernel(const uint8_t*, uint64_t, const uint64_t*, 
 __global__ void crc32_combine_kernel(const uint64_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
 __global__ void checksum_kernel(uint32_t, const uint8_t*, uint64_t, uint32_t, const uint32_t*,
                                 uint32_t, uint64_t*);
+template <uint32_t W, bool BITS, bool INV>
+__global__ void filter_kernel(const uint8_t*, uint64_t, uint32_t, const uint32_t*, uint32_t,
+                              uint8_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
 __global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
                             uint8_t*);
@@ -1296,6 +1299,68 @@ int bitar_hip_checksum(bitar_hip_ctx* ctx, void* stream, uint32_t kind, const vo
                      kind, static_cast<const uint8_t*>(d_data), n, seg, d_lens, nseg, d_sums);
   HIP_TRY(hipGetLastError(), "checksum launch");
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <uint32_t W>
+void launch_filter(bool bits, bool inv, uint32_t nseg, hipStream_t s, const uint8_t* in,
+                   uint64_t n, uint32_t seg, const uint32_t* lens, uint8_t* out) {
+  using Kernel = void (*)(const uint8_t*, uint64_t, uint32_t, const uint32_t*, uint32_t, uint8_t*);
+  const Kernel k = bits ? (inv ? bitar_hip::filter_kernel<W, true, true>
+                               : bitar_hip::filter_kernel<W, true, false>)
+                        : (inv ? bitar_hip::filter_kernel<W, false, true>
+                               : bitar_hip::filter_kernel<W, false, false>);
+  hipLaunchKernelGGL(k, dim3(nseg), dim3(256), 0, s, in, n, seg, lens, nseg, out);
+}
+
+int filter_impl(bitar_hip_ctx* ctx, void* stream, uint32_t filter, uint32_t width, const void* d_in,
+                uint64_t n, uint32_t seg, const uint32_t* d_lens, uint32_t nseg, void* d_out,
+                bool inv) {
+  if (int r = enter(ctx)) return r;
+  if (filter != BITAR_HIP_FILTER_SHUFFLE && filter != BITAR_HIP_FILTER_BITSHUFFLE)
+    return fail(BITAR_HIP_INVALID, "filter must be SHUFFLE or BITSHUFFLE");
+  if (width != 2 && width != 4 && width != 8 && width != 16)
+    return fail(BITAR_HIP_INVALID, "element width must be 2, 4, 8 or 16");
+  if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
+  if (n == 0 || nseg == 0) return 0;
+  if (!d_in || !d_out) return fail(BITAR_HIP_INVALID, "null buffer");
+  const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+  if (a < b ? b - a < n : a - b < n)
+    return fail(BITAR_HIP_INVALID, "filter input and output overlap");
+  // segments at or past n move nothing: launch only those that start inside the buffer
+  const uint64_t inside = (n + seg - 1) / seg;
+  if (inside < nseg) nseg = (uint32_t)inside;
+  const bool bits = filter == BITAR_HIP_FILTER_BITSHUFFLE;
+  hipStream_t s = pick_stream(ctx, stream);
+  const uint8_t* in = static_cast<const uint8_t*>(d_in);
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  switch (width) {
+    case 2: launch_filter<2>(bits, inv, nseg, s, in, n, seg, d_lens, out); break;
+    case 4: launch_filter<4>(bits, inv, nseg, s, in, n, seg, d_lens, out); break;
+    case 8: launch_filter<8>(bits, inv, nseg, s, in, n, seg, d_lens, out); break;
+    default: launch_filter<16>(bits, inv, nseg, s, in, n, seg, d_lens, out); break;
+  }
+  HIP_TRY(hipGetLastError(), "filter launch");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bitar_hip_filter_apply(bitar_hip_ctx* ctx, void* stream, uint32_t filter, uint32_t width,
+                           const void* d_in, uint64_t n, uint32_t seg, const uint32_t* d_lens,
+                           uint32_t nseg, void* d_out) {
+  return filter_impl(ctx, stream, filter, width, d_in, n, seg, d_lens, nseg, d_out, false);
+}
+
+int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, uint32_t width,
+                            const void* d_in, uint64_t n, uint32_t seg, const uint32_t* d_lens,
+                            uint32_t nseg, void* d_out) {
+  return filter_impl(ctx, stream, filter, width, d_in, n, seg, d_lens, nseg, d_out, true);
 }
 
 int bitar_hip_fill_at(bitar_hip_ctx* ctx, void* stream, int kind, uint64_t seed,

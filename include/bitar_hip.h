@@ -270,6 +270,40 @@ int bitar_hip_checksum(bitar_hip_ctx* ctx, void* stream, uint32_t kind, const vo
                        uint64_t n, uint32_t seg, const uint32_t* d_lens, uint32_t nseg,
                        uint64_t* d_sums);
 
+/* ---- filters for fixed-width column buffers ----
+ * A transposition of each segment on its own, in front of compress and behind decompress, so
+ * that the codecs' short windows see one byte (or bit) position of every element side by
+ * side.  S = the L bytes of a segment, w = the element width, 2, 4, 8 or 16 (a caller with
+ * 1-byte elements does not filter):
+ *   SHUFFLE     m = L / w;  T[j*m + i] = S[i*w + j] (i < m, j < w): Blosc shuffle / Parquet
+ *               BYTE_STREAM_SPLIT per segment.  The last L - m*w bytes keep their positions.
+ *   BITSHUFFLE  m8 = (L / w) & ~7;  plane p = 8*j + b (byte j of the element, bit b, LSB = 0)
+ *               occupies T[p*(m8/8), (p+1)*(m8/8)), and bit t of its byte q is bit b of
+ *               S[(8q + t)*w + j]: the HDF5 bitshuffle layout with one block per segment.  The
+ *               last L - m8*w bytes keep their positions.
+ * The output has the input's length.  No reference counterpart, and no stock library knows
+ * the filter: filter and width travel with the caller's frame like codec and segment size. */
+enum bitar_hip_filter { BITAR_HIP_FILTER_SHUFFLE = 1, BITAR_HIP_FILTER_BITSHUFFLE = 2 };
+
+/* Filter segment i of d_in (at d_in + i*seg) into d_out + i*seg.  Its length is d_lens[i], or
+ * min(seg, n - i*seg) with d_lens NULL (the convention of bitar_hip_checksum; nseg may be any
+ * count).  A length above min(seg, n - i*seg) -- BITAR_HIP_SEGMENT_ERROR of a failed op is
+ * one -- moves nothing and writes nothing for that segment (the failed op has already made the
+ * next sync fail).  Nothing past min(n, nseg*seg) is read or written, and the buffers may have
+ * any alignment.  Asynchronous on `stream`; n == 0 or nseg == 0 launches nothing.
+ * BITAR_HIP_INVALID (the context stays usable): an unknown filter, a width outside
+ * {2, 4, 8, 16}, seg outside [1, 65536], a null buffer, [d_in, d_in + n) overlapping
+ * [d_out, d_out + n). */
+int bitar_hip_filter_apply(bitar_hip_ctx* ctx, void* stream, uint32_t filter, uint32_t width,
+                           const void* d_in, uint64_t n, uint32_t seg, const uint32_t* d_lens,
+                           uint32_t nseg, void* d_out);
+
+/* The inverse, with the same arguments: d_in holds filtered segments (e.g. a decompress's
+ * output with d_lens = its d_produced), d_out receives the caller's bytes. */
+int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, uint32_t width,
+                            const void* d_in, uint64_t n, uint32_t seg, const uint32_t* d_lens,
+                            uint32_t nseg, void* d_out);
+
 /* ---- one gzip member (RFC 1952) from DEFLATE segments ----
  * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec:
  * BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
