@@ -17,6 +17,8 @@ CODEC_DEFLATE = 2
 CODEC_ZSTD = 3
 CODEC_DEFLATE_DYNAMIC = 4  # HuffmanEncoding::DYNAMIC (decoded as CODEC_DEFLATE)
 CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio operating point
+# INTPACK: frame-of-reference bit packing of 1 / 2 / 4 / 8-byte integers (any of them decodes)
+CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -140,6 +142,15 @@ def check(rc):
 
 def slot_size(codec, seg):
     return int(lib().bitar_hip_slot_size(codec, seg))
+
+
+def codec_intpack(width):
+    """the INTPACK codec id of an element width of 1, 2, 4 or 8 bytes"""
+    try:
+        return {1: CODEC_INTPACK8, 2: CODEC_INTPACK16, 4: CODEC_INTPACK32,
+                8: CODEC_INTPACK64}[width]
+    except (KeyError, TypeError):
+        raise ValueError(f"INTPACK element width must be 1, 2, 4 or 8, not {width!r}") from None
 
 
 def max_distance(codec):

@@ -85,7 +85,7 @@ class CompressDevice {
   [[nodiscard]] std::uint64_t slot_size() const noexcept { return slot_size_; }
   [[nodiscard]] void* stream(std::uint16_t queue_pair_id) const;
   /// log2 of the farthest match distance the configured encoder emits (12; 14 for the wide
-  /// LZ4 parse), set by Initialize.  configuration's window_size() is what was requested (or
+  /// LZ4 parse; 0 for INTPACK, which has no matches), set by Initialize.  configuration's window_size() is what was requested (or
   /// this value when 0 was), as in the reference.
   [[nodiscard]] std::uint8_t encoder_window() const noexcept { return encoder_window_; }
 
@@ -117,6 +117,9 @@ class CompressDevice {
     *filter = 0;
     *width = 0;
   }
+
+  /// The element width of Codec::INTPACK, in bytes.
+  [[nodiscard]] virtual std::uint32_t element_width() const { return 1; }
 
   [[nodiscard]] auto state() const noexcept { return state_; }
   void set_state(internal::DeviceState state) { state_ = state; }
@@ -177,6 +180,7 @@ class HipCompressDevice : public HipGfx950CompressDevice {
       std::unique_ptr<Configuration<Class_HIP_GFX950>> configuration) override;
   [[nodiscard]] std::uint32_t checksum_kind() const override;
   void filter_kind(std::uint32_t* filter, std::uint32_t* width) const override;
+  [[nodiscard]] std::uint32_t element_width() const override;
 
   friend arrow::Result<HipGfx950CompressDevice*>
   DeviceManager::Create<Class_HIP_GFX950>(std::uint8_t, std::vector<std::uint32_t>);

@@ -10,6 +10,7 @@ std::string_view ToString(Codec c) {
     case Codec::DEFLATE: return "DEFLATE";
     case Codec::LZ4: return "LZ4";
     case Codec::ZSTD: return "ZSTD";
+    case Codec::INTPACK: return "INTPACK";
   }
   return "UNKNOWN";
 }

@@ -293,9 +293,11 @@ bool OnDevice(std::uint64_t address, int device) {
 
 // DEFLATE + FIXED -> fixed-Huffman blocks; DEFLATE + DYNAMIC (the reference default,
 // config.h:151) or DEFAULT (the PMD's choice) -> dynamic Huffman
+// INTPACK -> the id of the configured element width
 template <typename Cfg>
-std::uint32_t AbiCodec(const Cfg& c) {
+std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
   switch (c.codec()) {
+    case Codec::INTPACK: return BITAR_HIP_CODEC_INTPACK(element_width);
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     default:
@@ -325,7 +327,7 @@ arrow::Status CompressDevice<Class, Enable>::PreAllocateMemory() {
   bitar_hip_config cfg{num_qps(), 0};
   BITAR_ABI(bitar_hip_open(device_id_, &cfg, &ctx_), "Device configuration failed");
   set_state(internal::DeviceState::kConfigured);
-  const auto codec = internal::AbiCodec(*configuration_);
+  const auto codec = internal::AbiCodec(*configuration_, element_width());
   const std::uint32_t seg = configuration_->decompressed_seg_size();
   slot_size_ = std::max<std::uint64_t>(bitar_hip_slot_size(codec, seg),
                                        (configuration_->compressed_seg_size() + 255u) & ~255u);
@@ -394,7 +396,7 @@ arrow::Result<BufferVector> CompressDevice<Class, Enable>::Compress(
   const std::uint32_t seg = configuration_->decompressed_seg_size();
   const auto n = static_cast<std::uint64_t>(decompressed_buffer->size());
   const auto nseg = static_cast<std::uint32_t>((n + seg - 1) / seg);
-  const auto codec = internal::AbiCodec(*configuration_);
+  const auto codec = internal::AbiCodec(*configuration_, element_width());
 
   // input: read HBM in place; host memory (the reference attaches it zero-copy, 380-399) is
   // staged into HBM chunk by chunk with each chunk's compress overlapping the next one's
@@ -551,7 +553,7 @@ arrow::Status CompressDevice<Class, Enable>::Decompress(
   } guard{this, queue_pair_id};
 
   const auto nseg = static_cast<std::uint32_t>(compressed_buffers.size());
-  const auto codec = internal::AbiCodec(*configuration_);
+  const auto codec = internal::AbiCodec(*configuration_, element_width());
   // op j decompresses buffers [j*k, (j+1)*k) as one stream into k segments of the output
   // (max_sgl_segs = k, reference memory.cc:432-505); k > 1 first joins the op's buffers in
   // the queue pair's chain scratch (the src mbuf chain)
@@ -762,7 +764,7 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   if (configuration_->burst_size() == 0)
     return arrow::Status::Invalid("Burst size must be greater than 0");
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
-      configuration_->codec() != Codec::ZSTD)
+      configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::INTPACK)
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
   if (configuration_->max_sgl_segs() < 1) configuration_->set_max_sgl_segs(1);
@@ -778,7 +780,16 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
     return arrow::Status::Invalid("decompressed_seg_size is not in the range of [",
                                   internal::kMinSegSize, ", ", internal::kMaxSegSize32, "]");
   }
-  // level: LZ4 1..9 (>= 2 selects the wide parse); DEFLATE and ZSTD have one level, so any
+  if (configuration_->codec() == Codec::INTPACK) {
+    const auto w = element_width();
+    if (w != 1 && w != 2 && w != 4 && w != 8)
+      return arrow::Status::Invalid("element_width (", w, ") of INTPACK must be 1, 2, 4 or 8");
+    // (a chained op would be one stream over k slots: the codec has no use for it)
+    if (configuration_->max_sgl_segs() > 1)
+      return arrow::Status::Invalid("INTPACK cannot be combined with chained operations "
+                                    "(max_sgl_segs > 1)");
+  }
+  // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
   // other value is refused rather than ignored (the reference always sets 1)
   if (configuration_->level() < 1 || configuration_->level() > 9)
     return arrow::Status::Invalid("level is not in the range of [1, 9]");
@@ -791,12 +802,16 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   // LZ4 / single-segment Zstd 2^16) is honoured -- every stream the encoder writes is valid for
   // it, and the decoders take the format's full window -- a smaller one is refused.
   // encoder_window() reports the reach whatever was requested.
-  const std::uint32_t reach = bitar_hip_max_distance(internal::AbiCodec(*configuration_));
+  const std::uint32_t reach =
+      bitar_hip_max_distance(internal::AbiCodec(*configuration_, element_width()));
   std::uint8_t window = 1;
   while ((1u << window) < reach) ++window;
   encoder_window_ = window;
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
-  if (configuration_->window_size() == 0) {
+  if (configuration_->codec() == Codec::INTPACK) {  // no matches, no window: ignored, reported 0
+    encoder_window_ = 0;
+    configuration_->set_window_size(0);
+  } else if (configuration_->window_size() == 0) {
     configuration_->set_window_size(window);
   } else if (configuration_->window_size() < window || configuration_->window_size() > max_window) {
     return arrow::Status::Invalid("window_size is not in the range of [", +window, ", ",
@@ -848,6 +863,8 @@ arrow::Status HipCompressDevice::ValidateConfiguration() {
     if (hip_configuration->max_sgl_segs() > 1)
       return arrow::Status::Invalid("A filter cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
+    if (hip_configuration->codec() == Codec::INTPACK)
+      return arrow::Status::Invalid("INTPACK takes no filter");
   }
   return HipGfx950CompressDevice::ValidateConfiguration();
 }
@@ -859,6 +876,11 @@ void HipCompressDevice::filter_kind(std::uint32_t* filter, std::uint32_t* width)
   if (!c || c->filter() == Filter::NONE) return;
   *filter = c->filter() == Filter::SHUFFLE ? BITAR_HIP_FILTER_SHUFFLE : BITAR_HIP_FILTER_BITSHUFFLE;
   *width = c->element_width();
+}
+
+std::uint32_t HipCompressDevice::element_width() const {
+  const auto* c = dynamic_cast<const HipConfiguration*>(configuration().get());
+  return c ? c->element_width() : 1;
 }
 
 std::uint32_t HipCompressDevice::checksum_kind() const {

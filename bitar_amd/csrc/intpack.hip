@@ -1,0 +1,456 @@
+// intpack.hip -- INTPACK: frame-of-reference bit packing of integer columns, per segment, both
+// directions (gfx950).  No reference counterpart and no match search: one pass finds, for the
+// plain values and for their deltas, a signed minimum per block of 256 elements and the bit
+// length of the largest residual per miniblock of 64; the smaller of the two forms is emitted.
+//
+// Stream of a segment of L bytes, element width W, m = L / W elements:
+//   byte 0      0x40 | mode << 2 | log2(W)     mode 0 packed, 1 packed with delta, 2 stored
+//   byte 1      0
+//   bytes 2..3  LE16(L - 1)
+//   stored:     L raw bytes
+//   packed:     [mode 1: element 0]  widths[nmb]  refs[nblk] (W bytes each)  payload  tail
+//               nmb = ceil(m / 64), nblk = ceil(nmb / 4); miniblock k's payload is 8 * widths[k]
+//               bytes, element t at bits [t*b, (t+1)*b) of the little-endian bit string
+//
+// One wavefront per segment, lane t = element t of the current miniblock.  The encoder reads
+// its segment twice (plan, then emit): the second read comes from L2 / Infinity Cache, and an
+// LDS copy of a 64 KiB segment would leave two waves per CU.  Element and payload addresses
+// have any alignment: loads take the aligned dwords that hold a needed byte and realign, the
+// payload leaves as aligned dwords with the bytes shared between two miniblocks carried over.
+#include "../../include/bitar_hip.h"
+#include "wave.hip.h"
+
+namespace bitar_hip {
+
+namespace ipk {
+
+constexpr uint32_t kMini = 64;     // elements per miniblock
+constexpr uint32_t kMaxMini = 1024;  // miniblocks of a 64 KiB segment of bytes
+constexpr uint32_t kMaxBlk = 256;
+
+template <uint32_t W> struct Elem { using U = uint32_t; using S = int32_t; };
+template <> struct Elem<8> { using U = uint64_t; using S = int64_t; };
+
+// v moved by a DPP control (lanes without a source, or outside the row mask, get `idle`)
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp(uint32_t v, uint32_t idle) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)idle, (int)v, CTRL, ROWS, 0xf, false);
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint64_t dpp(uint64_t v, uint64_t idle) {
+  const uint32_t lo = dpp<CTRL, ROWS>((uint32_t)v, (uint32_t)idle);
+  const uint32_t hi = dpp<CTRL, ROWS>((uint32_t)(v >> 32), (uint32_t)(idle >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint32_t lane63(uint32_t v) { return readlane(v, 63); }
+__device__ __forceinline__ uint64_t lane63(uint64_t v) {
+  return ((uint64_t)readlane((uint32_t)(v >> 32), 63) << 32) | readlane((uint32_t)v, 63);
+}
+
+// reductions over the wave's 64 lanes (the DPP ladder of wave_incl_sum; lane 63 holds the result)
+template <typename U>
+__device__ __forceinline__ U wave_or(U x) {
+  x |= dpp<0x111, 0xf>(x, (U)0);
+  x |= dpp<0x112, 0xf>(x, (U)0);
+  x |= dpp<0x114, 0xf>(x, (U)0);
+  x |= dpp<0x118, 0xf>(x, (U)0);
+  x |= dpp<0x142, 0xa>(x, (U)0);
+  x |= dpp<0x143, 0xc>(x, (U)0);
+  return lane63(x);
+}
+template <typename S>
+__device__ __forceinline__ S imin(S a, S b) { return a < b ? a : b; }
+template <typename S, typename U>
+__device__ __forceinline__ S wave_min(S v) {
+  constexpr U top = (U)(~(U)0 >> 1);  // the largest signed value: the identity
+  S x = v;
+  x = imin(x, (S)dpp<0x111, 0xf>((U)x, top));
+  x = imin(x, (S)dpp<0x112, 0xf>((U)x, top));
+  x = imin(x, (S)dpp<0x114, 0xf>((U)x, top));
+  x = imin(x, (S)dpp<0x118, 0xf>((U)x, top));
+  x = imin(x, (S)dpp<0x142, 0xa>((U)x, top));
+  x = imin(x, (S)dpp<0x143, 0xc>((U)x, top));
+  return (S)lane63((U)x);
+}
+template <typename U>
+__device__ __forceinline__ U wave_incl_add(U x) {
+  x += dpp<0x111, 0xf>(x, (U)0);
+  x += dpp<0x112, 0xf>(x, (U)0);
+  x += dpp<0x114, 0xf>(x, (U)0);
+  x += dpp<0x118, 0xf>(x, (U)0);
+  x += dpp<0x142, 0xa>(x, (U)0);
+  x += dpp<0x143, 0xc>(x, (U)0);
+  return x;
+}
+
+__device__ __forceinline__ uint32_t bit_length(uint32_t v) { return 32u - (uint32_t)__clz((int)v); }
+__device__ __forceinline__ uint32_t bit_length(uint64_t v) {
+  return 64u - (uint32_t)__clzll((long long)v);
+}
+
+// the W-byte little-endian element at p (any alignment): only aligned units that hold one of
+// its bytes are loaded
+template <uint32_t W>
+__device__ __forceinline__ typename Elem<W>::U load_elem(const GMEM uint8_t* p) {
+  const uint32_t a = (uint32_t)(uintptr_t)p;
+  if constexpr (W == 1) {
+    return *p;
+  } else if constexpr (W == 2) {
+    if ((a & 1u) == 0) return *reinterpret_cast<const GMEM uint16_t*>(p);
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8;
+  } else {
+    const GMEM uint32_t* q = reinterpret_cast<const GMEM uint32_t*>(p - (a & 3u));
+    if constexpr (W == 4) {
+      const uint32_t lo = q[0];
+      if ((a & 3u) == 0) return lo;
+      return funnel(lo, q[1], a);
+    } else {
+      uint32_t lo = q[0], hi = q[1];
+      if ((a & 3u) != 0) {
+        const uint32_t top = q[2];
+        lo = funnel(lo, hi, a);
+        hi = funnel(hi, top, a);
+      }
+      return ((uint64_t)hi << 32) | lo;
+    }
+  }
+}
+
+template <uint32_t W>
+__device__ __forceinline__ void store_elem(GMEM uint8_t* p, typename Elem<W>::U v) {
+  const uint32_t a = (uint32_t)(uintptr_t)p;
+  if constexpr (W == 1) {
+    *p = (uint8_t)v;
+  } else if constexpr (W == 2) {
+    if ((a & 1u) == 0) {
+      *reinterpret_cast<GMEM uint16_t*>(p) = (uint16_t)v;
+    } else {
+      p[0] = (uint8_t)v;
+      p[1] = (uint8_t)(v >> 8);
+    }
+  } else if ((a & 3u) == 0) {
+    GMEM uint32_t* q = reinterpret_cast<GMEM uint32_t*>(p);
+    q[0] = (uint32_t)v;
+    if constexpr (W == 8) q[1] = (uint32_t)(v >> 32);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < W; ++k) p[k] = (uint8_t)(v >> (8 * k));
+  }
+}
+
+// the x of this lane's element idx: the element (mode 0) or its difference to the one before
+// (mode 1), mod 2^(8W); lanes at or past m get 0
+template <uint32_t W>
+__device__ __forceinline__ void load_values(const GMEM uint8_t* src, uint32_t idx, uint32_t m,
+                                            typename Elem<W>::U& plain, typename Elem<W>::U& delta) {
+  using U = typename Elem<W>::U;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  const uint32_t lane = lane_id();
+  U v = 0;
+  if (idx < m) v = load_elem<W>(src + (uint64_t)idx * W);
+  U prev = dpp<0x138, 0xf>(v, (U)0);  // wave_shr:1
+  if (lane == 0 && idx > 0 && idx < m) prev = load_elem<W>(src + (uint64_t)(idx - 1) * W);
+  U d = (v - prev) & mask;
+  if (idx < kMini) {  // the first miniblock: x_0 = x_1, or 0 when there is no element 1
+    const U d1 = (U)__shfl(d, 1);
+    if (idx == 0) d = m > 1 ? d1 : 0;
+  }
+  plain = v;
+  delta = idx < m ? d : 0;
+}
+
+template <uint32_t W>
+__device__ __forceinline__ typename Elem<W>::S as_signed(typename Elem<W>::U x) {
+  using S = typename Elem<W>::S;
+  constexpr uint32_t sh = 8 * sizeof(S) - 8 * W;
+  return (S)(x << sh) >> sh;
+}
+
+struct Shared {
+  uint8_t wid[2][kMaxMini];                                // widths of mode 0 / mode 1
+  __attribute__((aligned(8))) uint8_t ref[2][kMaxBlk * 8]; // references, W bytes each
+  uint32_t stage[2 * kMini + 4];                           // one miniblock's bit string
+};
+
+template <uint32_t W>
+__device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32_t L,
+                                                 GMEM uint8_t* dst, uint32_t* size_out,
+                                                 Shared& sh) {
+  using U = typename Elem<W>::U;
+  using S = typename Elem<W>::S;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  constexpr uint32_t kLog = W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : 3;
+  const uint32_t lane = lane_id();
+  const uint32_t m = L / W, tail = L - m * W;
+  const uint32_t nmb = (m + kMini - 1) / kMini, nblk = (nmb + 3) / 4;
+
+  // ---- plan: both modes' references and widths in one sweep -------------------------------
+  uint32_t sum[2] = {0, 0};
+  for (uint32_t blk = 0; blk < nblk; ++blk) {
+    U x[2][4];
+    S lo[2] = {(S)(~(U)0 >> 1), (S)(~(U)0 >> 1)};
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const uint32_t idx = (blk * 4 + j) * kMini + lane;
+      load_values<W>(src, idx, m, x[0][j], x[1][j]);
+      if (idx < m) {
+        lo[0] = imin(lo[0], as_signed<W>(x[0][j]));
+        lo[1] = imin(lo[1], as_signed<W>(x[1][j]));
+      }
+    }
+#pragma unroll
+    for (uint32_t md = 0; md < 2; ++md) {
+      const U ref = (U)wave_min<S, U>(lo[md]) & mask;
+      if (lane == 0) {
+        if constexpr (W == 8) *reinterpret_cast<uint64_t*>(&sh.ref[md][blk * 8]) = ref;
+        else if constexpr (W == 4) *reinterpret_cast<uint32_t*>(&sh.ref[md][blk * 4]) = ref;
+        else if constexpr (W == 2) *reinterpret_cast<uint16_t*>(&sh.ref[md][blk * 2]) = (uint16_t)ref;
+        else sh.ref[md][blk] = (uint8_t)ref;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t k = blk * 4 + j;
+        const uint32_t idx = k * kMini + lane;
+        const U r = idx < m ? (U)((x[md][j] - ref) & mask) : (U)0;
+        const uint32_t b = bit_length(wave_or<U>(r));
+        if (k < nmb) {
+          if (lane == 0) sh.wid[md][k] = (uint8_t)b;
+          sum[md] += 8u * b;
+        }
+      }
+    }
+  }
+  lds_order();
+
+  // ---- mode: delta only when strictly smaller, stored when nothing is gained ---------------
+  const uint32_t fixed = 4u + nmb + nblk * W + tail;
+  const uint32_t size0 = fixed + sum[0], size1 = fixed + W + sum[1];
+  const uint32_t mode = size1 < size0 ? 1u : 0u;
+  const uint32_t total = mode ? size1 : size0;
+  GMEM uint32_t* head = reinterpret_cast<GMEM uint32_t*>(dst);  // (slots are 16-B aligned)
+  if (!(total < 4u + L)) {
+    if (lane == 0) {
+      *head = 0x40u | 2u << 2 | kLog | (L - 1) << 16;
+      *size_out = 4u + L;
+    }
+    wave_copy_global(dst + 4, src, L);
+    return;
+  }
+  if (lane == 0) {
+    *head = 0x40u | mode << 2 | kLog | (L - 1) << 16;
+    *size_out = total;
+  }
+  uint32_t pos = 4;
+  if (mode) {
+    if (lane < W) dst[pos + lane] = src[lane];
+    pos += W;
+  }
+  for (uint32_t k = lane; k < nmb; k += kWave) dst[pos + k] = sh.wid[mode][k];
+  pos += nmb;
+  for (uint32_t k = lane; k < nblk * W; k += kWave) dst[pos + k] = sh.ref[mode][k];
+  pos += nblk * W;
+
+  // ---- emit: the payload as aligned dwords; `a` bytes of every miniblock's last dword are ----
+  // ---- the first bytes of the next one's (miniblocks are multiples of 8 bytes)           ----
+  GMEM uint8_t* pay = dst + pos;
+  const uint32_t a = (uint32_t)(uintptr_t)pay & 3u;
+  uint32_t carry = 0, off = 0;
+  bool started = false;
+  for (uint32_t k = 0; k < nmb; ++k) {
+    const uint32_t b = sh.wid[mode][k];
+    if (b == 0) continue;
+    const uint32_t idx = k * kMini + lane;
+    U xs[2];
+    load_values<W>(src, idx, m, xs[0], xs[1]);
+    U ref;
+    if constexpr (W == 8) ref = *reinterpret_cast<const uint64_t*>(&sh.ref[mode][(k / 4) * 8]);
+    else if constexpr (W == 4) ref = *reinterpret_cast<const uint32_t*>(&sh.ref[mode][(k / 4) * 4]);
+    else if constexpr (W == 2) ref = *reinterpret_cast<const uint16_t*>(&sh.ref[mode][(k / 4) * 2]);
+    else ref = sh.ref[mode][k / 4];
+    const U r = idx < m ? (U)(((mode ? xs[1] : xs[0]) - ref) & mask) : (U)0;
+    // the bit string in LDS, shifted by the payload's byte misalignment
+    const uint32_t nd = 2 * b;  // its dwords; dword nd holds the bytes carried over
+    sh.stage[lane] = 0;
+    sh.stage[lane + kWave] = 0;
+    if (lane < 4) sh.stage[2 * kWave + lane] = 0;
+    lds_order();
+    if (lane == 0) sh.stage[0] = carry;
+    lds_order();
+    const uint32_t bit = 8 * a + lane * b;
+    const uint32_t d = bit >> 5, s = bit & 31u;
+    const uint64_t lo64 = (uint64_t)(uint32_t)r << s;
+    uint32_t w0 = (uint32_t)lo64, w1 = (uint32_t)(lo64 >> 32), w2 = 0;
+    if constexpr (W == 8) {
+      const uint64_t hi64 = (uint64_t)(uint32_t)(r >> 32) << s;
+      w1 |= (uint32_t)hi64;
+      w2 = (uint32_t)(hi64 >> 32);
+    }
+    if (w0) atomicOr(&sh.stage[d], w0);
+    if (w1) atomicOr(&sh.stage[d + 1], w1);
+    if (w2) atomicOr(&sh.stage[d + 2], w2);
+    lds_order();
+    GMEM uint32_t* q = reinterpret_cast<GMEM uint32_t*>(pay + off - a);
+    for (uint32_t j = lane; j < nd; j += kWave) {
+      const uint32_t v = sh.stage[j];
+      if (j == 0 && a && !started) {  // the payload's first dword: its low bytes are the header's
+        for (uint32_t t = a; t < 4; ++t) pay[t - a] = (uint8_t)(v >> (8 * t));
+      } else {
+        q[j] = v;
+      }
+    }
+    carry = sh.stage[nd];
+    lds_order();
+    started = true;
+    off += 8 * b;
+  }
+  if (started && lane < a) pay[off - a + lane] = (uint8_t)(carry >> (8 * lane));
+  if (lane < tail) pay[off + lane] = src[m * W + lane];
+}
+
+struct DecShared {
+  uint8_t wid[kMaxMini];
+  uint32_t off[kMaxMini];  // byte offset of every miniblock in the payload
+};
+
+// the packed form: src holds csize bytes, the header is valid and L <= seg.  Returns false for a
+// stream that must be rejected (checked before anything is written).
+template <uint32_t W>
+__device__ __forceinline__ bool decompress_packed(const GMEM uint8_t* src, uint32_t csize,
+                                                  uint32_t L, uint32_t mode, GMEM uint8_t* dst,
+                                                  DecShared& sh) {
+  using U = typename Elem<W>::U;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  const uint32_t lane = lane_id();
+  const uint32_t m = L / W, tail = L - m * W;
+  const uint32_t nmb = (m + kMini - 1) / kMini, nblk = (nmb + 3) / 4;
+  const uint32_t base_at = 4, wid_at = 4 + (mode ? W : 0), ref_at = wid_at + nmb;
+  const uint32_t pay_at = ref_at + nblk * W;
+  if (csize < pay_at + tail) return false;  // (so the header arrays lie inside the stream)
+
+  // widths -> offsets; the stream's size must be exactly what they add up to
+  uint32_t run = 0;
+  bool bad = false;
+  for (uint32_t k0 = 0; k0 < nmb; k0 += kWave) {
+    const uint32_t k = k0 + lane;
+    const uint32_t b = k < nmb ? src[wid_at + k] : 0u;
+    bad = bad || b > 8 * W;
+    const uint32_t incl = wave_incl_sum(8u * b);
+    if (k < nmb) {
+      sh.wid[k] = (uint8_t)b;
+      sh.off[k] = run + incl - 8u * b;
+    }
+    run += readlane(incl, 63);
+  }
+  if (ballot(bad) != 0) return false;  // (each width <= 64: run <= 64 KiB * 8, no overflow)
+  if (pay_at + run + tail != csize) return false;
+  lds_order();
+
+  const GMEM uint8_t* pay = src + pay_at;
+  U carry = 0;
+  for (uint32_t k = 0; k < nmb; ++k) {
+    const uint32_t b = sh.wid[k];
+    const uint32_t idx = k * kMini + lane;
+    U r = 0;
+    if (b) {
+      const GMEM uint8_t* p = pay + sh.off[k] + ((lane * b) >> 3);
+      const uint32_t al = (uint32_t)(uintptr_t)p & 3u;
+      const uint32_t s = 8 * al + ((lane * b) & 7u);  // < 32
+      const GMEM uint32_t* q = reinterpret_cast<const GMEM uint32_t*>(p - al);
+      // only the dwords that hold one of the field's bits (all inside the miniblock's bytes)
+      const uint32_t d0 = q[0];
+      const uint32_t d1 = s + b > 32 ? q[1] : 0u;
+      const uint64_t lo64 = ((uint64_t)d1 << 32) | d0;
+      if constexpr (W == 8) {
+        const uint32_t d2 = s + b > 64 ? q[2] : 0u;
+        r = lo64 >> s;
+        if (s) r |= (uint64_t)d2 << (64 - s);
+        if (b < 64) r &= ((uint64_t)1 << b) - 1;
+      } else {
+        r = (uint32_t)(lo64 >> s);
+        if (b < 32) r &= (1u << b) - 1;
+      }
+    }
+    const U ref = load_elem<W>(src + ref_at + (k / 4) * W);
+    U v = (r + ref) & mask;
+    if (mode) {
+      if (idx == 0) v = load_elem<W>(src + base_at);
+      v = wave_incl_add<U>(v) + carry;
+      carry = lane63(v);
+    }
+    if (idx < m) store_elem<W>(dst + (uint64_t)idx * W, v);
+  }
+  if (lane < tail) dst[m * W + lane] = pay[run + lane];
+  return true;
+}
+
+}  // namespace ipk
+
+// Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
+// or dsts[i]); sizes[i] = the stream's size (at most 4 + the segment's length: never a failure).
+template <uint32_t W>
+__global__ __launch_bounds__(64) void intpack_compress_kernel(
+    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
+    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
+  __shared__ ipk::Shared sh;
+  const uint32_t i = blockIdx.x;
+  const uint64_t seg_off = (uint64_t)i * seg;
+  if (seg_off >= n_total) return;
+  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
+  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
+  ipk::compress_segment<W>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
+}
+
+template __global__ void intpack_compress_kernel<1>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                    uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_kernel<2>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                    uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_kernel<4>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                    uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_kernel<8>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                    uint64_t, uint8_t* const*, uint32_t*);
+
+// Segment i: csizes[i] bytes at srcs[i] (or slab + i*slot_stride) -> out + i*seg; produced[i] =
+// its length, or BITAR_HIP_SEGMENT_ERROR (and bit 0 of the error word) for a stream the format
+// rejects.  The element width comes from the stream's tag.  Nothing outside the stream's
+// csizes[i] bytes is used (an aligned dword is loaded only when one of its bytes is), and
+// nothing outside the segment's seg bytes is written.
+__global__ __launch_bounds__(64) void intpack_decompress_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
+  __shared__ ipk::DecShared sh;
+  const uint32_t i = blockIdx.x;
+  if (i >= nseg) return;
+  const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
+  GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
+  const uint32_t csize = csizes[i];
+  bool ok = csize >= 4;
+  uint32_t L = 0;
+  if (ok) {
+    const uint32_t tag = src[0], rsv = src[1];
+    const uint32_t mode = (tag >> 2) & 3u;
+    L = 1u + src[2] + ((uint32_t)src[3] << 8);
+    ok = (tag >> 4) == 4u && mode != 3u && rsv == 0 && L <= seg;
+    if (ok && mode == 2) {
+      ok = csize == 4u + L;
+      if (ok) wave_copy_global(dst, src + 4, L);
+    } else if (ok) {
+      switch (tag & 3u) {
+        case 0: ok = ipk::decompress_packed<1>(src, csize, L, mode, dst, sh); break;
+        case 1: ok = ipk::decompress_packed<2>(src, csize, L, mode, dst, sh); break;
+        case 2: ok = ipk::decompress_packed<4>(src, csize, L, mode, dst, sh); break;
+        default: ok = ipk::decompress_packed<8>(src, csize, L, mode, dst, sh); break;
+      }
+    }
+  }
+  if (lane_id() == 0) {
+    if (ok) {
+      produced[i] = L;
+    } else {
+      produced[i] = BITAR_HIP_SEGMENT_ERROR;
+      atomicOr(err, 1u);
+    }
+  }
+}
+
+}  // namespace bitar_hip

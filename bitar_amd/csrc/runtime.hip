@@ -95,6 +95,12 @@ __global__ void checksum_kernel(uint32_t, const uint8_t*, uint64_t, uint32_t, co
 template <uint32_t W, bool BITS, bool INV>
 __global__ void filter_kernel(const uint8_t*, uint64_t, uint32_t, const uint32_t*, uint32_t,
                               uint8_t*);
+template <uint32_t W>
+__global__ void intpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
+                                        uint8_t* const*, uint32_t*);
+__global__ void intpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
+                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
+                                          uint32_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
 __global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
                             uint8_t*);
@@ -334,9 +340,16 @@ int bitar_hip_device(bitar_hip_ctx* ctx, int* device) {
   return 0;
 }
 
+// the four INTPACK ids, 8 + log2 of the element width
+static bool is_intpack(uint32_t codec) {
+  return codec >= BITAR_HIP_CODEC_INTPACK8 && codec <= BITAR_HIP_CODEC_INTPACK64;
+}
+
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
   uint64_t bound;
-  if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
+  if (is_intpack(codec))
+    bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
+  else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
   else if (codec == BITAR_HIP_CODEC_DEFLATE || codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC)
     bound = ((uint64_t)seg * 9 + 7) / 8 + 16u;          // fixed Huffman, 9 bits/literal
@@ -357,7 +370,11 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
     case BITAR_HIP_CODEC_DEFLATE_DYNAMIC:
     case BITAR_HIP_CODEC_ZSTD: return 4096u - 1536u;
     case BITAR_HIP_CODEC_LZ4_WIDE: return 16384u - 1536u;
-    default: return 0;
+    case BITAR_HIP_CODEC_INTPACK8:
+    case BITAR_HIP_CODEC_INTPACK16:
+    case BITAR_HIP_CODEC_INTPACK32:
+    case BITAR_HIP_CODEC_INTPACK64: return 0;  // "none": the codec has no matches at all
+    default: return 0;                          // "unknown": no such codec
   }
 }
 
@@ -492,7 +509,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (int r = enter(ctx)) return r;
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
-      codec != BITAR_HIP_CODEC_LZ4_WIDE)
+      codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -516,7 +533,18 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
                          cin, nb, seg, cn, keys);
     });
   };
-  if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
+  if (is_intpack(codec)) {
+    // one streaming kernel, the same work for every segment: plain order (intpack.hip)
+#define BITAR_INTPACK(W)                                                                      \
+  hipLaunchKernelGGL(bitar_hip::intpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, s, \
+                     in, n, seg, slab, slot_stride, dsts, d_sizes)
+    if (codec == BITAR_HIP_CODEC_INTPACK8) BITAR_INTPACK(1);
+    else if (codec == BITAR_HIP_CODEC_INTPACK16) BITAR_INTPACK(2);
+    else if (codec == BITAR_HIP_CODEC_INTPACK32) BITAR_INTPACK(4);
+    else BITAR_INTPACK(8);
+#undef BITAR_INTPACK
+  }
+  else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
     SegOrder ord;
     if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
     if (codec == BITAR_HIP_CODEC_LZ4)
@@ -872,8 +900,9 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const bool fixed_hint = codec == BITAR_HIP_CODEC_DEFLATE;
   if (codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC) codec = BITAR_HIP_CODEC_DEFLATE;  // same format
   if (codec == BITAR_HIP_CODEC_LZ4_WIDE) codec = BITAR_HIP_CODEC_LZ4;              // same format
-  if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
-      codec != BITAR_HIP_CODEC_ZSTD)
+  if (is_intpack(codec)) codec = BITAR_HIP_CODEC_INTPACK8;  // (the width is in each stream's tag)
+  if (codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_LZ4 &&
+      codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (nseg == 0) return 0;  // reference device.cc:244-246
   // Zstd: a segment may be a whole stock frame of up to kMaxZstdFrame bytes (the wave
@@ -893,7 +922,11 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const auto* srcs = reinterpret_cast<const uint8_t* const*>(d_srcs);
   const auto* slab = static_cast<const uint8_t*>(d_slab);
   auto* out = static_cast<uint8_t*>(d_out);
-  if (codec == BITAR_HIP_CODEC_LZ4)
+  if (codec == BITAR_HIP_CODEC_INTPACK8) {
+    hipLaunchKernelGGL(bitar_hip::intpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
+                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
+  }
+  else if (codec == BITAR_HIP_CODEC_LZ4)
   {
     // near-history kernel over every segment, then the far-history kernel over the segments
     // it deferred (lz4_decompress.hip)

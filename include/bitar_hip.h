@@ -46,13 +46,44 @@ enum bitar_hip_codec {
                                           reference default, config.h:151); decoded like
                                           DEFLATE.  Compress runs two kernels through a
                                           stream-ordered scratch allocation. */
-  BITAR_HIP_CODEC_LZ4_WIDE = 5         /* LZ4 blocks from the wide parse: 16 KiB history (match
+  BITAR_HIP_CODEC_LZ4_WIDE = 5,        /* LZ4 blocks from the wide parse: 16 KiB history (match
                                           distance <= 14848), 4096-entry table -- the ratio
                                           operating point, within a few % of liblz4's ratio
                                           at a lower speed; the streams are ordinary LZ4 blocks
                                           (decoded like LZ4).  The C++ front-end selects it for
                                           Codec::LZ4 at level() >= 2 (bitar/config.h). */
+  /* INTPACK: frame-of-reference bit packing of little-endian integer
+   * elements, for columns of narrow range (dictionary indices, small integers, sorted keys,
+   * timestamps, string offsets).  The id is 8 + log2(element width in bytes); no reference
+   * counterpart and no stock library reads the format.  One stream per segment of L bytes,
+   * m = L / w elements, the last L - m*w bytes are the tail:
+   *   byte 0      0x40 | mode << 2 | log2(w)    mode 0 packed, 1 packed with delta, 2 stored
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes
+   *   packed:     [mode 1: element 0, w bytes]
+   *               widths[nmb]  one byte (0..8w) per miniblock of 64 elements, nmb = ceil(m / 64)
+   *               refs[nblk]   one w-byte reference per block of 4 miniblocks
+   *               payload      miniblock k = 8 * widths[k] bytes: element t at bits [t*b, (t+1)*b)
+   *                            of a little-endian bit string, elements past m as 0
+   *               tail
+   * Values: x_i = v_i (mode 0) or v_i - v_(i-1) mod 2^(8w) (mode 1; x_0 = x_1, 0 when m = 1,
+   * ignored by the decoder, which starts from element 0).  ref = a block's smallest x read as
+   * signed, residual = x - ref mod 2^(8w), widths[k] = the bit length of the miniblock's
+   * largest residual.  The encoder takes mode 1 only when strictly smaller, and the stored form
+   * when the winner is not strictly smaller than 4 + L.  The decoder takes w from the tag (all
+   * four ids select it) and rejects: another tag, byte 1 != 0, L > seg, a width above 8w, a
+   * stream whose size is not exactly what its header and widths add up to. */
+  BITAR_HIP_CODEC_INTPACK8 = 8,
+  BITAR_HIP_CODEC_INTPACK16 = 9,
+  BITAR_HIP_CODEC_INTPACK32 = 10,
+  BITAR_HIP_CODEC_INTPACK64 = 11
 };
+
+/* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
+#define BITAR_HIP_CODEC_INTPACK(width) \
+  ((width) == 1 ? BITAR_HIP_CODEC_INTPACK8 : (width) == 2 ? BITAR_HIP_CODEC_INTPACK16 : \
+   (width) == 4 ? BITAR_HIP_CODEC_INTPACK32 : BITAR_HIP_CODEC_INTPACK64)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -105,13 +136,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound), rounded up to 256 B.  Plays the role of compressed_seg_size
+ * fixed-Huffman bound; seg + 4 for INTPACK, its stored form), rounded up to 256 B; 0 for an
+ * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK has no matches: its 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
@@ -305,8 +337,8 @@ int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, u
                             uint32_t nseg, void* d_out);
 
 /* ---- one gzip member (RFC 1952) from DEFLATE segments ----
- * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec:
- * BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
+ * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK
+ * included: BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
  * a coded segment up to and including its end-of-block code, 8 * d_sizes[i] for a stored
  * segment, BITAR_HIP_SEGMENT_ERROR for a failed one.  d_bits NULL: exactly
  * bitar_hip_compress.  The encoders guarantee: a coded segment is ONE block with BFINAL at bit
