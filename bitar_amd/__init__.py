@@ -19,6 +19,8 @@ CODEC_DEFLATE_DYNAMIC = 4  # HuffmanEncoding::DYNAMIC (decoded as CODEC_DEFLATE)
 CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio operating point
 # INTPACK: frame-of-reference bit packing of 1 / 2 / 4 / 8-byte integers (any of them decodes)
 CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
+# FLTPACK: decimal-scaled bit packing of 4-byte floats / 8-byte doubles (either id decodes both)
+CODEC_FLTPACK32, CODEC_FLTPACK64 = 18, 19
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -151,6 +153,14 @@ def codec_intpack(width):
                 8: CODEC_INTPACK64}[width]
     except (KeyError, TypeError):
         raise ValueError(f"INTPACK element width must be 1, 2, 4 or 8, not {width!r}") from None
+
+
+def codec_fltpack(width):
+    """the FLTPACK codec id of an element width of 4 (float32) or 8 (float64) bytes"""
+    try:
+        return {4: CODEC_FLTPACK32, 8: CODEC_FLTPACK64}[width]
+    except (KeyError, TypeError):
+        raise ValueError(f"FLTPACK element width must be 4 or 8, not {width!r}") from None
 
 
 def max_distance(codec):

@@ -45,7 +45,11 @@ using Class_HIP_GFX950 =
 /// frame-of-reference bit packing, with optional delta, of little-endian elements of
 /// HipConfiguration::element_width() bytes -- dictionary indices, small-range integers, sorted
 /// keys, timestamps, string offsets.
-enum class Codec : std::uint8_t { DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4 };
+/// FLTPACK is the engine's floating-point codec (likewise its own): values that
+/// are an integer over a power of ten -- prices, sensor readings, coordinates, integer-valued
+/// doubles -- are bit-packed as that integer, everything else is kept as an exception;
+/// element_width() is 4 (float) or 8 (double).
+enum class Codec : std::uint8_t { DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
 /// rte_comp_checksum_type
@@ -106,7 +110,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK has no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK and FLTPACK have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }
@@ -125,7 +129,7 @@ class Configuration {
 
   /// Compression level, 1..9 (rte_comp_compress_xform.level; the reference always sets 1,
   /// config.cc:86-88).  LZ4: 1 = the fast parse, >= 2 = the wide parse (16 KiB history, the
-  /// ratio operating point, BITAR_HIP_CODEC_LZ4_WIDE).  DEFLATE, ZSTD and INTPACK have one level.
+  /// ratio operating point, BITAR_HIP_CODEC_LZ4_WIDE).  The other codecs have one level.
   [[nodiscard]] auto level() const noexcept { return level_; }
   void set_level(std::uint8_t level) { level_ = level; }
 
@@ -179,8 +183,8 @@ class HipConfiguration : public Configuration<Class_HIP_GFX950> {
     filter_ = filter;
     element_width_ = element_width;
   }
-  /// The element width alone: what Codec::INTPACK packs (1, 2, 4 or 8 bytes; it takes no
-  /// filter).  The decoder reads the width from each stream, so only the compressing side needs it.
+  /// The element width alone: what Codec::INTPACK (1, 2, 4 or 8 bytes) and Codec::FLTPACK (4 or
+  /// 8 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it.
   void set_element_width(std::uint8_t element_width) { element_width_ = element_width; }
 
   static HipConfiguration Defaults() { return {}; }

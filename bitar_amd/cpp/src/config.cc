@@ -11,6 +11,7 @@ std::string_view ToString(Codec c) {
     case Codec::LZ4: return "LZ4";
     case Codec::ZSTD: return "ZSTD";
     case Codec::INTPACK: return "INTPACK";
+    case Codec::FLTPACK: return "FLTPACK";
   }
   return "UNKNOWN";
 }

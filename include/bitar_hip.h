@@ -77,13 +77,49 @@ enum bitar_hip_codec {
   BITAR_HIP_CODEC_INTPACK8 = 8,
   BITAR_HIP_CODEC_INTPACK16 = 9,
   BITAR_HIP_CODEC_INTPACK32 = 10,
-  BITAR_HIP_CODEC_INTPACK64 = 11
+  BITAR_HIP_CODEC_INTPACK64 = 11,
+  /* FLTPACK: decimal-scaled bit packing of little-endian IEEE float (w = 4) or
+   * double (w = 8) elements, for columns that are decimal by origin (prices, sensor readings,
+   * coordinates, percentages, integer-valued doubles).  The id is 16 + log2(w); no reference
+   * counterpart and no stock library reads the format.  One stream per segment of L bytes,
+   * m = L / w elements, the last L - m*w bytes are the tail:
+   *   byte 0      0x50 | mode << 2 | log2(w)    mode 0 packed, 2 stored
+   *   byte 1      e, the decimal exponent, 0..15 (0 in the stored form)
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes
+   *   packed:     LE16 nx      number of exceptions, nx <= m
+   *               widths[nmb]  one byte (0..8w) per miniblock of 64 elements, nmb = ceil(m / 64)
+   *               refs[nblk]   one w-byte signed reference per block of 4 miniblocks
+   *               payload      miniblock k = 8 * widths[k] bytes: element t at bits [t*b, (t+1)*b)
+   *                            of a little-endian bit string (INTPACK's packing)
+   *               pos[nx]      LE16 element indices, strictly increasing, each < m
+   *               val[nx]      the exceptions' raw w-byte elements, in the same order
+   *               tail
+   *   size = 6 + nmb + nblk*w + 8*sum(widths) + nx*(2 + w) + (L - m*w)
+   * An element v is encodable at e when t = rint((double)v * 10^e) is finite, |t| <= 2^53
+   * (w = 8) or 2^31 - 1 (w = 4), and (double)n / 10^e for n = (int)t -- rounded to float for
+   * w = 4 -- has exactly v's bit pattern; every other element (NaN, infinities, -0.0, denormals,
+   * non-decimal values) is an exception.  ref = a block's smallest n over its encodable
+   * elements (0 without any), residual = n - ref mod 2^(8w), 0 at an exception's slot and past
+   * m.  The encoder picks e by a cost estimate over every 16th element (the smallest e among
+   * equals) and takes the stored form when the packed one is not strictly smaller than 4 + L.
+   * The decoder takes w from the tag (both ids select it) and rejects: another tag, mode 1 or
+   * 3, log2(w) below 2, e > 15 (e != 0 when stored), L > seg, nx > m, a width above 8w, a
+   * position >= m or not above the one before, a stream whose size is not exactly the formula
+   * (4 + L when stored).  Anything else decodes: arithmetic is mod 2^(8w), residuals at
+   * exception slots are ignored. */
+  BITAR_HIP_CODEC_FLTPACK32 = 18,
+  BITAR_HIP_CODEC_FLTPACK64 = 19
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
 #define BITAR_HIP_CODEC_INTPACK(width) \
   ((width) == 1 ? BITAR_HIP_CODEC_INTPACK8 : (width) == 2 ? BITAR_HIP_CODEC_INTPACK16 : \
    (width) == 4 ? BITAR_HIP_CODEC_INTPACK32 : BITAR_HIP_CODEC_INTPACK64)
+
+/* The FLTPACK id of an element width of 4 (float) or 8 (double) bytes. */
+#define BITAR_HIP_CODEC_FLTPACK(width) \
+  ((width) == 4 ? BITAR_HIP_CODEC_FLTPACK32 : BITAR_HIP_CODEC_FLTPACK64)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -136,14 +172,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, its stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK and FLTPACK, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK has no matches: its 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK and FLTPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
@@ -337,7 +373,7 @@ int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, u
                             uint32_t nseg, void* d_out);
 
 /* ---- one gzip member (RFC 1952) from DEFLATE segments ----
- * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK
+ * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK and FLTPACK
  * included: BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
  * a coded segment up to and including its end-of-block code, 8 * d_sizes[i] for a stored
  * segment, BITAR_HIP_SEGMENT_ERROR for a failed one.  d_bits NULL: exactly
