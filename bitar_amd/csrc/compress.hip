@@ -33,19 +33,25 @@ __device__ __forceinline__ uint32_t lane_sel(uint64_t m, uint32_t a, uint32_t b)
 // The parse hands each window's matches over as sequence records {match start, distance,
 // length}: the chain lanes append them to an LDS list (one store, one mbcnt).  Every <= 64
 // records (and before the tail) one flush turns them into LZ4 sequences, one record per
-// lane: literal run = [previous match end, match start), sizes by one prefix sum, and then
-// the output is GATHERED 64 bytes per step -- output byte o finds its sequence (the latest one
-// starting at or before o: sequence starts marked in LDS, a prefix max), fetches that
-// sequence's packed header fields (ds_bpermute) and writes exactly one byte: token, length
-// byte, literal (from the input ring), offset byte or match-length byte.  Rare sequences --
-// literal run >= 270 bytes or outside the input ring, match >= 274 bytes -- and a flush that
-// would overrun the slot take the general path, one sequence at a time.
+// lane: literal run = [previous match end, match start), sizes by one prefix sum.  Then each
+// record lane stores its sequence's header bytes itself (token, length bytes, offset: they
+// are per-sequence work), and the literal bytes are GATHERED 64 per step -- literal j finds its
+// run (run starts marked in LDS, one compare and a v_mbcnt pair), fetches that run's packed
+// ring indices (one ds_bpermute) and copies one byte from the input ring to its place in the
+// output ring.  (Until DESIGN 4.17 every OUTPUT byte was gathered, header bytes included:
+// BITAR_LZ4_GATHER=2.)  Rare sequences -- literal run >= 270 bytes or outside the input
+// ring, match >= 274 bytes -- and a flush that would overrun the slot take the general path,
+// one sequence at a time.
 // Round 3's per-window emitter wrote six bytes per POSITION lane (token, length bytes,
 // offset, literal; trash bytes for the rest) after two prefix scans per window; with the
 // emitter removed the parse ran 30 % faster (1 GiB kinds 1 / 5 / 6), so that is what this
 // batching takes aim at.  The output bytes are the same.
+// BITAR_LZ4_GATHER: 3 = the record lanes store their own header bytes and only the literals
+// are gathered (the default); 2 = every output byte gathered (A/B runs); 1 = round 4's form.
+// BITAR_LZ4_OBUF: the staging ring; 1024 B would hold a typical kind-1 flush (~437 B) in one
+// chunk but measured 2.7 % slower than the parent where 512 B is 4.1 % faster.
 #ifndef BITAR_LZ4_GATHER
-#define BITAR_LZ4_GATHER 2
+#define BITAR_LZ4_GATHER 3
 #endif
 #ifndef BITAR_LZ4_OBUF
 #define BITAR_LZ4_OBUF 512
@@ -53,7 +59,9 @@ __device__ __forceinline__ uint32_t lane_sel(uint64_t m, uint32_t a, uint32_t b)
 constexpr uint32_t kLz4Obuf = BITAR_LZ4_OBUF;  // output ring (flushed to HBM in 16-B blocks)
 constexpr uint32_t kSeqCap = 64;    // records per flush (a window adds <= 16)
 struct Lz4Lds {
-#if BITAR_LZ4_GATHER == 2
+#if BITAR_LZ4_GATHER == 3
+  uint8_t ring[kLz4Obuf + 16];     // + one trash byte (padded)
+#elif BITAR_LZ4_GATHER == 2
   uint8_t ring[kLz4Obuf];          // (the gather writes every lane's byte inside the room)
 #else
   uint8_t ring[kLz4Obuf + kWave];  // + one trash byte per lane
@@ -124,7 +132,108 @@ struct Lz4Out : ByteOutT<kLz4Obuf> {
     if (ml >= 15) put_ext(ml - 15);
   }
 
-#if BITAR_LZ4_GATHER == 2
+#if BITAR_LZ4_GATHER == 3
+  // records of lanes [lo, hi) (all ordinary) as LZ4 sequences; false (nothing written) if they
+  // would overrun the slot.  A sequence's header bytes (token, literal-length byte, offset,
+  // match-length byte) are per-sequence work: its record lane holds them and stores them
+  // itself, five byte stores for the whole wave.  Only the literal bytes are gathered, 64 per
+  // step, as SeqCollect::gather (zstd_compress.hip) gathers them, except that a run's bytes
+  // go to that run's place in the output instead of a contiguous area.
+  //  * one scan of e | lit_len << 16 (e = the sequence's size) gives each sequence's output
+  //    offset a and its literal prefix lp (both < 2^16: <= 64 records of < 275 bytes);
+  //  * the range is cut into chunks of consecutive records whose output fits the staging
+  //    ring's room (kLz4Obuf - 64); room is made once per chunk;
+  //  * per literal step (u = literal counter + 1; lane t holds literal R + t): the non-empty
+  //    runs starting in the step mark their first literal (LDS, cleared once read), one
+  //    compare gives the start mask, a v_mbcnt pair the run's rank among the non-empty runs
+  //    (empty runs would share a start), and one ds_bpermute fetches the run's packed word
+  //    (input-ring index - u | output-ring index - u << 16; compacted by rank once per call);
+  //    lanes past the chunk's last literal store to the trash byte.
+  __device__ __forceinline__ bool bulk(const InRing& I, uint32_t lo, uint32_t hi, uint32_t q,
+                                       uint32_t lit_start, uint32_t off, uint32_t mlen) {
+    constexpr uint32_t kTrash = kLz4Obuf, kLim = kLz4Obuf - 64;
+    const uint32_t lane = lane_id();
+    const bool in = (lane >= lo) & (lane < hi);
+    const uint32_t lit_len = q - lit_start, ml = mlen - kMinMatch;
+    const uint32_t nlx = lit_len >= 15 ? 1u : 0u, nmx = ml >= 15 ? 1u : 0u;
+    const uint32_t e = in ? (3u + nlx + nmx + lit_len) | (lit_len << 16) : 0u;
+    const uint32_t incl = wave_incl_sum(e);
+    const uint32_t total = readlane(incl, kWave - 1) & 0xFFFFu;
+    if ((uint64_t)op + total > cap) return false;
+    const uint32_t excl = incl - e;
+    const uint32_t a = excl & 0xFFFFu, lp = excl >> 16;  // output offset, literals before
+    const uint32_t iend = incl & 0xFFFFu;
+    // the header bytes' ring indices (per byte: the ring wraps)
+    const uint32_t tok = ((lit_len < 15 ? lit_len : 15) << 4) | (ml < 15 ? ml : 15);
+    const uint32_t tA = (uint32_t)(uintptr_t)dst + op + a;
+    const uint32_t tO = tA + 1u + nlx + lit_len;
+    const uint32_t x0 = tA & kMask, x1 = (tA + 1u) & kMask;
+    const uint32_t x2 = tO & kMask, x3 = (tO + 1u) & kMask, x4 = (tO + 2u) & kMask;
+    const uint64_t lxm = ballot(nlx != 0u), mxm = ballot(nmx != 0u);
+    // the non-empty literal runs: ring indices less u, compacted by rank (ds_permute; the
+    // other lanes' words go to lane 63, which no rank reaches unless all 64 runs are non-empty)
+    const bool ne = in & (lit_len != 0u);
+    const uint64_t nem = ballot(ne);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(nem >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)nem, 0u));
+    const uint32_t Din = I.in_lo + lit_start - lp - 1u;
+    const uint32_t Dout = tA + nlx - lp;
+    const uint32_t Pc = (uint32_t)__builtin_amdgcn_ds_permute(
+        (int)((ne ? rank : kWave - 1) << 2), (int)((Din & 0xFFFFu) | (Dout << 16)));
+    const uint32_t lp4 = ne ? lp << 2 : 0x7FFFFF00u;  // mark slot x4 (others: the trash slot)
+    const uint32_t mark = lp + 1u;
+    const uint32_t zero = 0;
+    uint32_t u = lane + 1u;
+    uint32_t before = 0;          // non-empty runs starting before the step
+    uint32_t c0 = lo, ba = 0, bl = 0;  // the chunk's first record, its a and lp
+    do {
+      // the chunk: records [c0, c1) end within kLim bytes of its start (one always does)
+      const uint64_t over = ballot(iend > ba + kLim);
+      uint32_t c1 = over ? (uint32_t)__builtin_ctzll(over) : kWave;
+      c1 = c1 < hi ? c1 : hi;
+      c1 = c1 > c0 ? c1 : c0 + 1u;  // (a sequence is < 275 bytes: never taken)
+      const uint32_t end = readlane(incl, c1 - 1);
+      const uint32_t ea = end & 0xFFFFu, el = end >> 16;
+      // (the slot's capacity was checked for the whole range: only the staging ring's room)
+      if (op + (ea - ba) - flushed > kLim) flush(op, false);
+      lds_order();
+      const uint64_t cm = ((c1 < kWave ? 1ull << c1 : 0ull) - 1ull) & ~((1ull << c0) - 1ull);
+      ring[lane_sel(cm, x0, kTrash)] = (uint8_t)tok;
+      ring[lane_sel(cm & lxm, x1, kTrash)] = (uint8_t)(lit_len - 15u);
+      ring[lane_sel(cm, x2, kTrash)] = (uint8_t)off;
+      ring[lane_sel(cm, x3, kTrash)] = (uint8_t)(off >> 8);
+      ring[lane_sel(cm & mxm, x4, kTrash)] = (uint8_t)(ml - 15u);
+      for (uint32_t R = bl; R < el; R += kWave) {
+        const uint32_t nb = el - R < kWave ? el - R : kWave;
+        const uint64_t vm = nb < kWave ? (1ull << nb) - 1ull : ~0ull;
+        lds_order();
+        const uint32_t slot = min(lp4 - (R << 2), (uint32_t)kWave << 2);
+        *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(L->marks) + slot) = mark;
+        lds_order();
+        const uint32_t mk = L->marks[lane];
+        L->marks[lane] = zero;
+        // (a run starting past the chunk's last literal belongs to the next chunk)
+        const uint64_t S = ballot(mk == u) & vm;
+        const uint32_t base = before - 1u + (uint32_t)(S & 1u);
+        const uint64_t S1 = S >> 1;
+        const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(S1 >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)S1, 0u));
+        before += (uint32_t)__builtin_popcountll(S);
+        const uint32_t p = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((k << 2) + (base << 2)),
+                                                                  (int)Pc);
+        const uint32_t b = I.ring[(p + u) & I.mask];
+        ring[lane_sel(vm, ((p >> 16) + u) & kMask, kTrash)] = (uint8_t)b;
+        u += nb;
+      }
+      lds_order();
+      op += ea - ba;
+      ba = ea;
+      bl = el;
+      c0 = c1;
+    } while (c0 < hi);
+    return true;
+  }
+#elif BITAR_LZ4_GATHER == 2
   // records of lanes [lo, hi) (all ordinary) as LZ4 sequences, gathered 64 output bytes per
   // step; false (nothing written) if they would overrun the slot.
   // Per step (u = output byte + 1, vs op; lane t holds byte R + t):
