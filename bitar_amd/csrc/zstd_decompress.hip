@@ -384,6 +384,9 @@ __device__ __forceinline__ int huf_read(State& s, uint8_t* win, Tabs& t, uint32_
         break;
       }
     }
+    // at most 255 weights are sent (the last symbol's is implied): a 256th would put the
+    // implied one past wts[] (the oracle's zs_huf_read rejects the same)
+    if (nw > 255) return -1;
     used = 1 + (int)hb;
   } else {  // direct 4-bit weights
     nw = hb - 127;
@@ -1130,7 +1133,7 @@ __device__ uint32_t multi_blocks(State& s, uint8_t* win, uint32_t p, uint32_t cs
     const uint32_t bh = load_le(s, win, p, 3);
     const uint32_t last = bh & 1u, type = (bh >> 1) & 3u, bsz = bh >> 3;
     p += 3;
-    if (type != 2 || bsz > (128u << 10) || bsz < 2 || p + bsz > cs) return 0;
+    if (type != 2 || bsz > (128u << 10) || bsz < 3 || p + bsz > cs) return 0;
     if (nb > 0) {
       const uint32_t end = p + bsz;
       const uint32_t b0 = load_le(s, win, p, 1);
@@ -1426,7 +1429,8 @@ __global__ __launch_bounds__(64) BITAR_ZSD_ATTR void zstd_decompress_kernel(
         out_fill(s, ring, load_le(s, win, p, 1), bsz);
         p += 1;
       } else if (type == 2) {
-        if (bsz > (128u << 10) || p + bsz > cs) { bad = true; break; }
+        // (at least 3 bytes: libzstd's MIN_CBLOCK_SIZE, oracle/bitar_zstd.c)
+        if (bsz < 3 || bsz > (128u << 10) || p + bsz > cs) { bad = true; break; }
         ZP_BEGIN(tb);
         const int r = block(s, win, ring, t, fr, p, bsz, hand, last || nbm != 0, fsz, (uint32_t)fcs,
                             h_nseq, h_regen);

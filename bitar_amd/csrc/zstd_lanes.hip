@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64) void zstd_lanes_kernel(
         bool ok = type != 3;
         if (type == 0) ok = p + bsz <= cs && (uint64_t)op + bsz <= cap;
         else if (type == 1) ok = p + 1 <= cs && (uint64_t)op + bsz <= cap;
-        else if (type == 2) ok = bsz <= (128u << 10) && p + bsz <= cs;
+        else if (type == 2) ok = bsz >= 3 && bsz <= (128u << 10) && p + bsz <= cs;
         if (!ok) {
           active = false;
           produced[i] = kDefer;

@@ -97,6 +97,9 @@ uint64_t bo_xxh64(const uint8_t* p, uint64_t len, uint64_t seed);
 /* tests: why the last bo_zstd_decompress on this thread rejected (0: another reason) */
 #define BO_ZSTD_REJECT_HUF_END 1      /* a Huffman stream not consumed exactly (detail: bits left) */
 #define BO_ZSTD_REJECT_SEQ_OVERREAD 2 /* the sequence bitstream read past its start */
+#define BO_ZSTD_REJECT_SEQ_LEFTOVER 3 /* bits left in it after the last sequence (detail: bits) */
+#define BO_ZSTD_REJECT_MODE_BITS 4    /* reserved bits set in the Symbol_Compression_Modes byte */
+#define BO_ZSTD_REJECT_NOT_ONE_FRAME 5 /* a skippable frame in front, or bytes behind the frame */
 int bo_zstd_last_reject(int64_t* detail);
 /* Encode one segment as one Zstandard frame, exactly as the HIP kernel does (bitar
  * window-scan parse; blocks of <= 512 sequences; raw literals; predefined FSE sequence

@@ -284,6 +284,7 @@ static int zs_huf_read(zs_huf* h, const uint8_t* src, uint32_t len) {
       s2 = f.t[s2].base + (uint32_t)zs_read(&b, f.t[s2].nbits);
       if (b.pos < 0) { w[nw++] = (uint8_t)f.t[s1].sym; break; }
     }
+    if (nw > 255) return -1;  /* at most 255 weights are sent: the last one is implied */
     used = 1 + (int)hb;
   } else {  /* direct 4-bit weights */
     nw = hb - 127;
@@ -482,7 +483,7 @@ static int zs_block(zs_ctx* z, const uint8_t* src, uint32_t len, uint8_t* dst, u
     if (nseq) {
       if (p >= len) goto out;
       const uint32_t modes = src[p++];
-      if (modes & 3) goto out;
+      if (modes & 3) { g_zs_reject = BO_ZSTD_REJECT_MODE_BITS; goto out; }
       uint32_t used;
       if (zs_table(&z->ll, &z->have_ll, modes >> 6, kLLDefault, 35, ZS_LL_AL, 35, 9, src + p, len - p, &used)) goto out;
       p += used;
@@ -534,6 +535,10 @@ static int zs_block(zs_ctx* z, const uint8_t* src, uint32_t len, uint8_t* dst, u
         op += ml;
       }
       if (b.pos == 0) goto seq_done;
+      if (b.pos > 0) {  /* every sequence decoded and executed, bits left over */
+        g_zs_reject = BO_ZSTD_REJECT_SEQ_LEFTOVER;
+        g_zs_reject_detail = b.pos;
+      }
     seq_fail:
       if (b.pos < 0) { /* the sequence bitstream was read past its start */
         g_zs_reject = BO_ZSTD_REJECT_SEQ_OVERREAD;
@@ -560,6 +565,7 @@ int bo_zstd_decompress(const uint8_t* src, uint32_t csize, uint8_t* dst, uint32_
                        uint32_t* produced) {
   g_zs_reject = 0;
   g_zs_reject_detail = 0;
+  if (csize >= 4 && (rd32le(src) & 0xFFFFFFF0u) == 0x184D2A50u) g_zs_reject = BO_ZSTD_REJECT_NOT_ONE_FRAME;
   if (csize < 6 || rd32le(src) != 0xFD2FB528u) return BO_ERR_IO;
   uint32_t p = 4;
   const uint32_t fhd = src[p++];
@@ -607,7 +613,9 @@ int bo_zstd_decompress(const uint8_t* src, uint32_t csize, uint8_t* dst, uint32_
       op += bsz;
       p += 1;
     } else if (type == 2) {
-      if (bsz > (128u << 10) || p + bsz > csize) goto done;
+      /* a compressed block holds at least 3 bytes (libzstd's MIN_CBLOCK_SIZE: the smallest
+       * literals header it writes is followed by a sequence count, and it rejects less) */
+      if (bsz < 3 || bsz > (128u << 10) || p + bsz > csize) goto done;
       if (zs_block(z, src + p, bsz, dst, cap, op, &op)) goto done;
       p += bsz;
     } else {
@@ -620,7 +628,10 @@ int bo_zstd_decompress(const uint8_t* src, uint32_t csize, uint8_t* dst, uint32_
     if ((uint32_t)bo_xxh64(dst, op, 0) != rd32le(src + p)) goto done;
     p += 4;
   }
-  if (p != csize) goto done;            /* one frame per segment */
+  if (p != csize) {                     /* one frame per segment */
+    g_zs_reject = BO_ZSTD_REJECT_NOT_ONE_FRAME;
+    goto done;
+  }
   if (has_fcs && fcs != op) goto done;
   *produced = op;
   rc = BO_OK;

@@ -21,7 +21,10 @@ named classes (anything else fails the test):
     test passes BIT_DStream_overflow), whose values then differ from any RFC 8878 reading.
 Rules the oracle took from the stock decoders through this test: zlib's inflate_table
 completeness rule for dynamic codes, liblz4's end-of-block conditions and its two
-length-extension input limits, libzstd's "weight-1 codes come in pairs" Huffman rule."""
+length-extension input limits, libzstd's "weight-1 codes come in pairs" Huffman rule; and,
+through the hand-built frames of tests/test_zstd_frames.py (which names three more classes:
+zstd_seq_leftover, zstd_mode_reserved_bits, zstd_one_frame_per_segment), libzstd's minimum of
+3 bytes for a compressed block."""
 import ctypes
 import zlib
 
