@@ -21,6 +21,8 @@ CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio
 CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
 # FLTPACK: decimal-scaled bit packing of 4-byte floats / 8-byte doubles (either id decodes both)
 CODEC_FLTPACK32, CODEC_FLTPACK64 = 18, 19
+# DICTPACK: per-segment dictionary + bit-packed indices of 4 / 8 / 16-byte elements (any id decodes)
+CODEC_DICTPACK32, CODEC_DICTPACK64, CODEC_DICTPACK128 = 26, 27, 28
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -161,6 +163,14 @@ def codec_fltpack(width):
         return {4: CODEC_FLTPACK32, 8: CODEC_FLTPACK64}[width]
     except (KeyError, TypeError):
         raise ValueError(f"FLTPACK element width must be 4 or 8, not {width!r}") from None
+
+
+def codec_dictpack(width):
+    """the DICTPACK codec id of an element width of 4, 8 or 16 bytes"""
+    try:
+        return {4: CODEC_DICTPACK32, 8: CODEC_DICTPACK64, 16: CODEC_DICTPACK128}[width]
+    except (KeyError, TypeError):
+        raise ValueError(f"DICTPACK element width must be 4, 8 or 16, not {width!r}") from None
 
 
 def max_distance(codec):

@@ -12,6 +12,7 @@ std::string_view ToString(Codec c) {
     case Codec::ZSTD: return "ZSTD";
     case Codec::INTPACK: return "INTPACK";
     case Codec::FLTPACK: return "FLTPACK";
+    case Codec::DICTPACK: return "DICTPACK";
   }
   return "UNKNOWN";
 }

@@ -107,6 +107,12 @@ __global__ void fltpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint
 __global__ void fltpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                           const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                           uint32_t*);
+template <uint32_t W>
+__global__ void dictpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
+                                         uint8_t* const*, uint32_t*);
+__global__ void dictpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
+                                           const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
+                                           uint32_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
 __global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
                             uint8_t*);
@@ -356,9 +362,14 @@ static bool is_fltpack(uint32_t codec) {
   return codec == BITAR_HIP_CODEC_FLTPACK32 || codec == BITAR_HIP_CODEC_FLTPACK64;
 }
 
+// the three DICTPACK ids, 24 + log2 of the element width (4, 8 or 16 bytes)
+static bool is_dictpack(uint32_t codec) {
+  return codec >= BITAR_HIP_CODEC_DICTPACK32 && codec <= BITAR_HIP_CODEC_DICTPACK128;
+}
+
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
   uint64_t bound;
-  if (is_intpack(codec) || is_fltpack(codec))
+  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec))
     bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
@@ -386,7 +397,10 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
     case BITAR_HIP_CODEC_INTPACK32:
     case BITAR_HIP_CODEC_INTPACK64:
     case BITAR_HIP_CODEC_FLTPACK32:
-    case BITAR_HIP_CODEC_FLTPACK64: return 0;  // "none": the codec has no matches at all
+    case BITAR_HIP_CODEC_FLTPACK64:
+    case BITAR_HIP_CODEC_DICTPACK32:
+    case BITAR_HIP_CODEC_DICTPACK64:
+    case BITAR_HIP_CODEC_DICTPACK128: return 0;  // "none": the codec has no matches at all
     default: return 0;                          // "unknown": no such codec
   }
 }
@@ -522,7 +536,8 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (int r = enter(ctx)) return r;
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
-      codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec) && !is_fltpack(codec))
+      codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec) && !is_fltpack(codec) &&
+      !is_dictpack(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -565,6 +580,16 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
     else
       hipLaunchKernelGGL(bitar_hip::fltpack_compress_kernel<8>, dim3((uint32_t)nseg), dim3(64), 0,
                          s, in, n, seg, slab, slot_stride, dsts, d_sizes);
+  }
+  else if (is_dictpack(codec)) {
+    // likewise (dictpack.hip)
+#define BITAR_DICTPACK(W)                                                                      \
+  hipLaunchKernelGGL(bitar_hip::dictpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, \
+                     s, in, n, seg, slab, slot_stride, dsts, d_sizes)
+    if (codec == BITAR_HIP_CODEC_DICTPACK32) BITAR_DICTPACK(4);
+    else if (codec == BITAR_HIP_CODEC_DICTPACK64) BITAR_DICTPACK(8);
+    else BITAR_DICTPACK(16);
+#undef BITAR_DICTPACK
   }
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
     SegOrder ord;
@@ -924,7 +949,9 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   if (codec == BITAR_HIP_CODEC_LZ4_WIDE) codec = BITAR_HIP_CODEC_LZ4;              // same format
   if (is_intpack(codec)) codec = BITAR_HIP_CODEC_INTPACK8;  // (the width is in each stream's tag)
   if (is_fltpack(codec)) codec = BITAR_HIP_CODEC_FLTPACK32;  // (likewise)
+  if (is_dictpack(codec)) codec = BITAR_HIP_CODEC_DICTPACK32;  // (likewise)
   if (codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
+      codec != BITAR_HIP_CODEC_DICTPACK32 &&
       codec != BITAR_HIP_CODEC_LZ4 &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
@@ -952,6 +979,10 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   }
   else if (codec == BITAR_HIP_CODEC_FLTPACK32) {
     hipLaunchKernelGGL(bitar_hip::fltpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
+                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
+  }
+  else if (codec == BITAR_HIP_CODEC_DICTPACK32) {
+    hipLaunchKernelGGL(bitar_hip::dictpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
                        slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
   }
   else if (codec == BITAR_HIP_CODEC_LZ4)

@@ -109,7 +109,38 @@ enum bitar_hip_codec {
    * (4 + L when stored).  Anything else decodes: arithmetic is mod 2^(8w), residuals at
    * exception slots are ignored. */
   BITAR_HIP_CODEC_FLTPACK32 = 18,
-  BITAR_HIP_CODEC_FLTPACK64 = 19
+  BITAR_HIP_CODEC_FLTPACK64 = 19,
+  /* DICTPACK: a per-segment dictionary plus bit-packed indices, for columns of
+   * wide values with few distinct ones (hash or surrogate ids, UUIDs, decimal128, floats that
+   * take a few hundred values, anything a Parquet reader decoded from a dictionary page).  The
+   * id is 24 + log2(w) for w = 4, 8 or 16 bytes (24 and 25 are not offered: INTPACK serves 1-
+   * and 2-byte elements); no reference counterpart and no stock library reads the format.  One
+   * stream per segment of L bytes, m = L / w elements compared as byte patterns (+0.0, -0.0
+   * and every NaN payload are distinct values), the last L - m*w bytes are the tail:
+   *   byte 0      0x60 | mode << 3 | log2(w)    mode 0 packed, 1 stored; log2(w) 2, 3 or 4
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                           size = 4 + L
+   *   packed:     LE16(d - 1)  d = number of dictionary entries, 1 <= d <= min(m, 1024)
+   *               dict[d]      the distinct elements, w bytes each, in order of first occurrence
+   *               payload      nmb = ceil(m / 64) miniblocks of 8*b bytes, b = bit_length(d - 1)
+   *                            (none when d = 1): element t's dictionary index at bits
+   *                            [t*b, (t+1)*b) of the miniblock's little-endian bit string
+   *                            (INTPACK's packing), slots past m written as 0
+   *               tail
+   *   size = 6 + d*w + 8*b*nmb + (L - m*w)
+   * The encoder packs a segment that has at most 1024 distinct elements and whose packed size is
+   * below 4 + L, and stores every other one (m = 0 included).  The two sizes differ by 2 mod 4,
+   * so they are never equal: "below" and "not above" are the same rule.  The decoder takes w
+   * from the tag (all three ids select it) and rejects, before it writes anything: a high nibble
+   * other than 6, log2(w) outside 2..4, byte 1 != 0, L > seg, d > min(m, 1024), a stream whose
+   * size is not exactly the formula (4 + L when stored).  An index >= d in one of the slots
+   * 0..m-1 rejects the segment as well, where the decoder meets it: the elements of the
+   * miniblocks before that one have been written then.  Bits in slots past m are ignored and
+   * duplicate dictionary entries are accepted. */
+  BITAR_HIP_CODEC_DICTPACK32 = 26,
+  BITAR_HIP_CODEC_DICTPACK64 = 27,
+  BITAR_HIP_CODEC_DICTPACK128 = 28
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -120,6 +151,11 @@ enum bitar_hip_codec {
 /* The FLTPACK id of an element width of 4 (float) or 8 (double) bytes. */
 #define BITAR_HIP_CODEC_FLTPACK(width) \
   ((width) == 4 ? BITAR_HIP_CODEC_FLTPACK32 : BITAR_HIP_CODEC_FLTPACK64)
+
+/* The DICTPACK id of an element width of 4, 8 or 16 bytes. */
+#define BITAR_HIP_CODEC_DICTPACK(width) \
+  ((width) == 4 ? BITAR_HIP_CODEC_DICTPACK32 : (width) == 8 ? BITAR_HIP_CODEC_DICTPACK64 : \
+   BITAR_HIP_CODEC_DICTPACK128)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -172,14 +208,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK and FLTPACK, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK and DICTPACK, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK and FLTPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK and DICTPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
@@ -373,7 +409,7 @@ int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, u
                             uint32_t nseg, void* d_out);
 
 /* ---- one gzip member (RFC 1952) from DEFLATE segments ----
- * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK and FLTPACK
+ * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK, FLTPACK and DICTPACK
  * included: BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
  * a coded segment up to and including its end-of-block code, 8 * d_sizes[i] for a stored
  * segment, BITAR_HIP_SEGMENT_ERROR for a failed one.  d_bits NULL: exactly
