@@ -23,6 +23,9 @@ CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
 CODEC_FLTPACK32, CODEC_FLTPACK64 = 18, 19
 # DICTPACK: per-segment dictionary + bit-packed indices of 4 / 8 / 16-byte elements (any id decodes)
 CODEC_DICTPACK32, CODEC_DICTPACK64, CODEC_DICTPACK128 = 26, 27, 28
+# RUNPACK: per-segment run lengths of 1 / 2 / 4 / 8 / 16-byte elements (any id decodes)
+CODEC_RUNPACK8, CODEC_RUNPACK16, CODEC_RUNPACK32, CODEC_RUNPACK64, CODEC_RUNPACK128 = \
+    32, 33, 34, 35, 36
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -171,6 +174,15 @@ def codec_dictpack(width):
         return {4: CODEC_DICTPACK32, 8: CODEC_DICTPACK64, 16: CODEC_DICTPACK128}[width]
     except (KeyError, TypeError):
         raise ValueError(f"DICTPACK element width must be 4, 8 or 16, not {width!r}") from None
+
+
+def codec_runpack(width):
+    """the RUNPACK codec id of an element width of 1, 2, 4, 8 or 16 bytes"""
+    try:
+        return {1: CODEC_RUNPACK8, 2: CODEC_RUNPACK16, 4: CODEC_RUNPACK32, 8: CODEC_RUNPACK64,
+                16: CODEC_RUNPACK128}[width]
+    except (KeyError, TypeError):
+        raise ValueError(f"RUNPACK element width must be 1, 2, 4, 8 or 16, not {width!r}") from None
 
 
 def max_distance(codec):

@@ -13,6 +13,7 @@ std::string_view ToString(Codec c) {
     case Codec::INTPACK: return "INTPACK";
     case Codec::FLTPACK: return "FLTPACK";
     case Codec::DICTPACK: return "DICTPACK";
+    case Codec::RUNPACK: return "RUNPACK";
   }
   return "UNKNOWN";
 }

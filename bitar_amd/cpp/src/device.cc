@@ -293,13 +293,14 @@ bool OnDevice(std::uint64_t address, int device) {
 
 // DEFLATE + FIXED -> fixed-Huffman blocks; DEFLATE + DYNAMIC (the reference default,
 // config.h:151) or DEFAULT (the PMD's choice) -> dynamic Huffman
-// INTPACK, FLTPACK, DICTPACK -> the id of the configured element width
+// INTPACK, FLTPACK, DICTPACK, RUNPACK -> the id of the configured element width
 template <typename Cfg>
 std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
   switch (c.codec()) {
     case Codec::INTPACK: return BITAR_HIP_CODEC_INTPACK(element_width);
     case Codec::FLTPACK: return BITAR_HIP_CODEC_FLTPACK(element_width);
     case Codec::DICTPACK: return BITAR_HIP_CODEC_DICTPACK(element_width);
+    case Codec::RUNPACK: return BITAR_HIP_CODEC_RUNPACK(element_width);
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     default:
@@ -767,7 +768,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
     return arrow::Status::Invalid("Burst size must be greater than 0");
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
       configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::INTPACK &&
-      configuration_->codec() != Codec::FLTPACK && configuration_->codec() != Codec::DICTPACK)
+      configuration_->codec() != Codec::FLTPACK && configuration_->codec() != Codec::DICTPACK &&
+      configuration_->codec() != Codec::RUNPACK)
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
   if (configuration_->max_sgl_segs() < 1) configuration_->set_max_sgl_segs(1);
@@ -808,6 +810,14 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
       return arrow::Status::Invalid("DICTPACK cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
   }
+  if (configuration_->codec() == Codec::RUNPACK) {
+    const auto w = element_width();
+    if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
+      return arrow::Status::Invalid("element_width (", w, ") of RUNPACK must be 1, 2, 4, 8 or 16");
+    if (configuration_->max_sgl_segs() > 1)
+      return arrow::Status::Invalid("RUNPACK cannot be combined with chained operations "
+                                    "(max_sgl_segs > 1)");
+  }
   // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
   // other value is refused rather than ignored (the reference always sets 1)
   if (configuration_->level() < 1 || configuration_->level() > 9)
@@ -828,7 +838,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   encoder_window_ = window;
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
   if (configuration_->codec() == Codec::INTPACK || configuration_->codec() == Codec::FLTPACK ||
-      configuration_->codec() == Codec::DICTPACK) {  // no matches, no window: ignored, reported 0
+      configuration_->codec() == Codec::DICTPACK ||
+      configuration_->codec() == Codec::RUNPACK) {  // no matches, no window: ignored, reported 0
     encoder_window_ = 0;
     configuration_->set_window_size(0);
   } else if (configuration_->window_size() == 0) {
@@ -889,6 +900,8 @@ arrow::Status HipCompressDevice::ValidateConfiguration() {
       return arrow::Status::Invalid("FLTPACK takes no filter");
     if (hip_configuration->codec() == Codec::DICTPACK)
       return arrow::Status::Invalid("DICTPACK takes no filter");
+    if (hip_configuration->codec() == Codec::RUNPACK)
+      return arrow::Status::Invalid("RUNPACK takes no filter");
   }
   return HipGfx950CompressDevice::ValidateConfiguration();
 }

@@ -1,0 +1,572 @@
+// runpack.hip -- RUNPACK: per-segment run-length coding of fixed-width elements, for sorted or
+// clustered columns whose values come in long runs (partition and dimension keys, coarse
+// timestamps, status and flag bytes, byte-per-value validity), both directions (gfx950).  No
+// reference counterpart.
+//
+// Stream of a segment of L bytes, element width W in {1, 2, 4, 8, 16}, m = L / W elements
+// compared as byte patterns:
+//   byte 0      0x70 | mode << 3 | log2(W)     mode 0 runs, 1 stored
+//   byte 1      bl, bytes per run length: 1 or 2 (0 in the stored form)
+//   bytes 2..3  LE16(L - 1)
+//   stored:     L raw bytes                                                  size = 4 + L
+//   runs:       LE16(r - 1)  values[r] (W bytes each)  lengths[r] (length - 1, bl bytes LE)  tail
+//               size = 6 + r*(W + bl) + (L - m*W)
+// Runs are maximal, bl is 1 when no run is longer than 256, and the runs form is taken when its
+// size is strictly below 4 + L (a tie is stored).
+//
+// One wavefront per segment.  Both kernels work in CHUNKS: chunk c is bytes [16c, 16c + 16) of
+// the segment, E = 16 / W whole elements, and lane t of a step holds chunk 64*step + t, so a
+// step moves 1 KiB at every width.  The encoder counts the runs in one pass and keeps the first
+// heads in LDS; a segment with more of them than fit there is read a second time to emit.  A step
+// without a head -- the common case of the columns this codec is for -- costs the load, the
+// compare and one ballot in either pass.  The
+// decoder builds chunks from the runs and stores them as 16-byte blocks aligned in the OUTPUT,
+// whatever the alignment of the segment.
+#include "../../include/bitar_hip.h"
+#include "bitpack.hip.h"
+
+namespace bitar_hip {
+
+namespace rpk {
+
+__device__ __forceinline__ uint32_t pick(const uint4& v, uint32_t k) {  // (no indexed registers)
+  return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
+}
+
+// bytes [s, s + 16) of the 32-byte little-endian pair (x, y), s in 0..16 and wave-uniform
+__device__ __forceinline__ uint4 window16(const uint4& x, const uint4& y, uint32_t s) {
+  const uint32_t r = s;  // (funnel keeps the low two bits)
+  switch (s >> 2) {
+    case 0: return make_uint4(funnel(x.x, x.y, r), funnel(x.y, x.z, r), funnel(x.z, x.w, r), funnel(x.w, y.x, r));
+    case 1: return make_uint4(funnel(x.y, x.z, r), funnel(x.z, x.w, r), funnel(x.w, y.x, r), funnel(y.x, y.y, r));
+    case 2: return make_uint4(funnel(x.z, x.w, r), funnel(x.w, y.x, r), funnel(y.x, y.y, r), funnel(y.y, y.z, r));
+    case 3: return make_uint4(funnel(x.w, y.x, r), funnel(y.x, y.y, r), funnel(y.y, y.z, r), funnel(y.z, y.w, r));
+    default: return y;
+  }
+}
+
+// every lane gets the lane below's v; lane 0 gets `carry` (wave-uniform)
+__device__ __forceinline__ uint4 from_below(const uint4& v, const uint4& carry) {
+  uint4 p = make_uint4(wave_shr1(v.x), wave_shr1(v.y), wave_shr1(v.z), wave_shr1(v.w));
+  if (lane_id() == 0) p = carry;
+  return p;
+}
+__device__ __forceinline__ uint4 lane63(const uint4& v) {
+  return make_uint4(readlane(v.x, 63), readlane(v.y, 63), readlane(v.z, 63), readlane(v.w, 63));
+}
+
+// The segment's chunks, for a segment at any address: aligned 16-byte blocks, a lane's second
+// block taken from the lane above.  A block is loaded only when it holds a byte of the segment.
+struct ChunkReader {
+  const GMEM uint4* sa;
+  uint32_t sh, L;
+  __device__ __forceinline__ ChunkReader(const GMEM uint8_t* src, uint32_t L_)
+      : sh((uint32_t)(uintptr_t)src & 15u), L(L_) {
+    sa = reinterpret_cast<const GMEM uint4*>(src - sh);
+  }
+  // chunk c of this lane (zeros where c starts past the segment; bytes past L are arbitrary)
+  __device__ __forceinline__ uint4 load(uint32_t c) const {
+    const bool act = 16u * c < L;
+    uint4 x = make_uint4(0, 0, 0, 0);
+    if (act) x = sa[c];
+    if (sh == 0) return x;
+    uint4 y = make_uint4(shfl_down1(x.x), shfl_down1(x.y), shfl_down1(x.z), shfl_down1(x.w));
+    // the block above: from the lane above when that lane loaded it, else from memory when it
+    // holds a byte of the segment (it starts at byte 16(c+1) - sh of it)
+    const bool own = lane_id() == kWave - 1 || !(16u * (c + 1) < L);
+    if (act && own && 16u * (c + 1) < L + sh) y = sa[c + 1];
+    return window16(x, y, sh);
+  }
+};
+
+// bit j: element j of chunk `ch` differs from its predecessor (element 0's is the last element
+// of `prev`, the chunk before)
+template <uint32_t W>
+__device__ __forceinline__ uint32_t head_mask(const uint4& ch, const uint4& prev) {
+  if constexpr (W == 16) {
+    return (((ch.x ^ prev.x) | (ch.y ^ prev.y) | (ch.z ^ prev.z) | (ch.w ^ prev.w)) != 0) ? 1u : 0u;
+  } else if constexpr (W == 8) {
+    const uint32_t a = (ch.x ^ prev.z) | (ch.y ^ prev.w), b = (ch.z ^ ch.x) | (ch.w ^ ch.y);
+    return (a ? 1u : 0u) | (b ? 2u : 0u);
+  } else if constexpr (W == 4) {
+    return (ch.x != prev.w ? 1u : 0u) | (ch.y != ch.x ? 2u : 0u) | (ch.z != ch.y ? 4u : 0u) |
+           (ch.w != ch.z ? 8u : 0u);
+  } else {
+    const uint32_t w[5] = {prev.w, ch.x, ch.y, ch.z, ch.w};
+    uint32_t mask = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      // every element of the dword against the one before it, 8*W bits down the byte string
+      const uint32_t d = w[k + 1] ^ (w[k + 1] << (8 * W) | w[k] >> (32 - 8 * W));
+      if constexpr (W == 2) {
+        mask |= ((d & 0xFFFFu) ? 1u : 0u) << (2 * k) | ((d >> 16) ? 2u : 0u) << (2 * k);
+      } else {
+        // bit 7 of each byte that is not 0, then those four bits gathered by a multiply
+        // (partial products land on distinct bits: 3, 10, 17, 24 | 11, 18, 25 | 19, 26 | 27)
+        const uint32_t t = (((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
+        mask |= (((t >> 7) * 0x01020408u) >> 24) << (4 * k);
+      }
+    }
+    return mask;
+  }
+}
+
+// element j of a chunk, in the low dwords of the result
+template <uint32_t W>
+__device__ __forceinline__ uint4 element(const uint4& ch, uint32_t j) {
+  if constexpr (W == 16) return ch;
+  else if constexpr (W == 8) return j ? make_uint4(ch.z, ch.w, 0, 0) : make_uint4(ch.x, ch.y, 0, 0);
+  else if constexpr (W == 4) return make_uint4(pick(ch, j), 0, 0, 0);
+  else if constexpr (W == 2) return make_uint4((pick(ch, j >> 1) >> (16 * (j & 1u))) & 0xFFFFu, 0, 0, 0);
+  else return make_uint4((pick(ch, j >> 2) >> (8 * (j & 3u))) & 0xFFu, 0, 0, 0);
+}
+
+// a run's value into the stream (values start 6 bytes into a 16-B aligned slot: elements of 4
+// bytes and more sit at 2 mod 4 and get halfword and dword stores)
+template <uint32_t W>
+__device__ __forceinline__ void store_value(GMEM uint8_t* p, const uint4& v) {
+  const uint32_t a = (uint32_t)(uintptr_t)p;
+  if constexpr (W == 1) {
+    *p = (uint8_t)v.x;
+  } else if constexpr (W == 2) {
+    if ((a & 1u) == 0) {
+      *reinterpret_cast<GMEM uint16_t*>(p) = (uint16_t)v.x;
+    } else {
+      p[0] = (uint8_t)v.x;
+      p[1] = (uint8_t)(v.x >> 8);
+    }
+  } else {
+    constexpr uint32_t N = W / 4;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    if ((a & 3u) == 2) {
+      *reinterpret_cast<GMEM uint16_t*>(p) = (uint16_t)w[0];
+      GMEM uint32_t* q = reinterpret_cast<GMEM uint32_t*>(p + 2);
+#pragma unroll
+      for (uint32_t k = 0; k + 1 < N; ++k) q[k] = w[k] >> 16 | w[k + 1] << 16;
+      *reinterpret_cast<GMEM uint16_t*>(p + W - 2) = (uint16_t)(w[N - 1] >> 16);
+    } else if ((a & 3u) == 0) {
+      GMEM uint32_t* q = reinterpret_cast<GMEM uint32_t*>(p);
+#pragma unroll
+      for (uint32_t k = 0; k < N; ++k) q[k] = w[k];
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < W; ++k) p[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3u)));
+    }
+  }
+}
+
+// (length - 1) of a run, bl bytes little-endian, wherever it falls
+__device__ __forceinline__ void store_length(GMEM uint8_t* p, uint32_t v, uint32_t bl) {
+  if (bl == 1) {
+    *p = (uint8_t)v;
+  } else if (((uint32_t)(uintptr_t)p & 1u) == 0) {
+    *reinterpret_cast<GMEM uint16_t*>(p) = (uint16_t)v;
+  } else {
+    p[0] = (uint8_t)v;
+    p[1] = (uint8_t)(v >> 8);
+  }
+}
+
+__device__ __forceinline__ void store_header(GMEM uint8_t* dst, uint32_t mode, uint32_t lg,
+                                             uint32_t bl, uint32_t L) {
+  // (slots are 16-B aligned)
+  *reinterpret_cast<GMEM uint32_t*>(dst) = 0x70u | mode << 3 | lg | bl << 8 | (L - 1) << 16;
+}
+
+// One step of either encoder pass: this lane's chunk, its head bits, and where the heads are.
+template <uint32_t W>
+struct HeadScan {
+  static constexpr uint32_t E = 16 / W;
+  ChunkReader rd;
+  uint32_t m;
+  uint4 carry = make_uint4(0, 0, 0, 0);  // the chunk of lane 63 of the step before
+  uint32_t last = 0;                     // position of the last head so far (element 0 is one)
+  uint4 ch;
+  uint32_t mask;
+
+  __device__ __forceinline__ HeadScan(const GMEM uint8_t* src, uint32_t L, uint32_t m_)
+      : rd(src, L), m(m_) {}
+
+  // loads the step's chunks; returns false when none of its elements is a head
+  __device__ __forceinline__ bool step(uint32_t c) {
+    ch = rd.load(c);
+    const uint4 prev = from_below(ch, carry);
+    carry = lane63(ch);
+    mask = head_mask<W>(ch, prev);
+    if (c == 0) mask |= 1u;
+    const uint32_t e0 = c * E;
+    const uint32_t nv = e0 >= m ? 0u : (m - e0 < E ? m - e0 : E);  // elements of the segment
+    mask &= (1u << nv) - 1u;
+    return ballot(mask != 0) != 0;
+  }
+  // (after a step with heads) the position of the last head below this lane's chunk, and the
+  // new `last`
+  __device__ __forceinline__ uint32_t head_below(uint32_t c) {
+    const uint32_t top = mask ? c * E + (31u - (uint32_t)__clz((int)mask)) + 1u : 0u;
+    const uint32_t incl = wave_incl_max(top);
+    const uint32_t below = max(wave_shr1(incl), last + 1u) - 1u;
+    last = readlane(incl, 63) - 1u;
+    return below;
+  }
+};
+
+// The heads pass one meets, while there are at most kCap of them: their positions and values.
+// A segment of long runs -- what the codec is for -- is then written from here and read once.
+// (A second read is a second read from HBM at scale: the 8192 segments in flight are 512 MiB,
+// twice the Infinity Cache.)  kCap keeps the LDS of a one-wave workgroup at 6 KiB or less.
+template <uint32_t W>
+struct EncShared {
+  static constexpr uint32_t kCap = W <= 4 ? 1024 : 256;
+  __attribute__((aligned(16))) uint32_t val[kCap * W / 4];
+  uint16_t pos[kCap];  // (a position is below 65536)
+
+  __device__ __forceinline__ void put(uint32_t k, uint32_t at, const uint4& v) {
+    pos[k] = (uint16_t)at;
+    if constexpr (W == 16) *reinterpret_cast<uint4*>(&val[4 * k]) = v;
+    else if constexpr (W == 8) *reinterpret_cast<uint2*>(&val[2 * k]) = make_uint2(v.x, v.y);
+    else if constexpr (W == 4) val[k] = v.x;
+    else if constexpr (W == 2) reinterpret_cast<uint16_t*>(val)[k] = (uint16_t)v.x;
+    else reinterpret_cast<uint8_t*>(val)[k] = (uint8_t)v.x;
+  }
+  __device__ __forceinline__ uint4 value(uint32_t k) const {
+    if constexpr (W == 16) return *reinterpret_cast<const uint4*>(&val[4 * k]);
+    else if constexpr (W == 8) return make_uint4(val[2 * k], val[2 * k + 1], 0, 0);
+    else if constexpr (W == 4) return make_uint4(val[k], 0, 0, 0);
+    else if constexpr (W == 2) return make_uint4(reinterpret_cast<const uint16_t*>(val)[k], 0, 0, 0);
+    else return make_uint4(reinterpret_cast<const uint8_t*>(val)[k], 0, 0, 0);
+  }
+};
+
+template <uint32_t W>
+__device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32_t L,
+                                                 GMEM uint8_t* dst, uint32_t* size_out,
+                                                 EncShared<W>& sh) {
+  constexpr uint32_t kCap = EncShared<W>::kCap;
+  constexpr uint32_t E = 16 / W;
+  constexpr uint32_t kLog = W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : W == 8 ? 3 : 4;
+  const uint32_t lane = lane_id();
+  const uint32_t m = L / W, tail = L - m * W;
+  const uint32_t nch = (m * W + 15u) / 16u;
+
+  // ---- pass one: the number of runs, and whether one is longer than 256 ---------------------
+  uint32_t r = 0, bl = 1;
+  bool stored = m == 0;
+  if (!stored) {
+    HeadScan<W> hs(src, L, m);
+    bool wide = false;
+    for (uint32_t c0 = 0; c0 < nch; c0 += kWave) {
+      const uint32_t c = c0 + lane;
+      if (!hs.step(c)) continue;
+      const uint32_t below = hs.head_below(c);
+      // the run that ends at this lane's first head (runs inside a chunk are shorter than 16)
+      const uint32_t first = c * E + (uint32_t)__builtin_ctz(hs.mask | 0x10000u);
+      if (ballot((hs.mask != 0) & (first - below > 256u)) != 0) wide = true;
+      const uint32_t cnt = (uint32_t)__popc(hs.mask);
+      const uint32_t incl = wave_incl_sum(cnt);
+      if (r < kCap) {  // head k, when it is one of the first kCap, is kept
+        uint32_t k = r + incl - cnt;
+        for (uint32_t mk = hs.mask; mk; mk &= mk - 1u, ++k) {
+          const uint32_t j = (uint32_t)__builtin_ctz(mk);
+          if (k < kCap) sh.put(k, c * E + j, element<W>(hs.ch, j));
+        }
+      }
+      r += readlane(incl, 63);
+      // the smallest runs form of r runs is no smaller than the stored one: no need to go on
+      if (6u + r * (W + 1u) >= 4u + L) {
+        stored = true;
+        break;
+      }
+    }
+    if (!stored) {
+      if (m - hs.last > 256u) wide = true;
+      bl = wide ? 2u : 1u;
+      stored = !(6u + r * (W + bl) + tail < 4u + L);  // a tie is stored
+    }
+  }
+  if (stored) {
+    if (lane == 0) {
+      store_header(dst, 1, kLog, 0, L);
+      *size_out = 4u + L;
+    }
+    wave_copy_global(dst + 4, src, L);
+    return;
+  }
+
+  if (lane == 0) {
+    store_header(dst, 0, kLog, bl, L);
+    *reinterpret_cast<GMEM uint16_t*>(dst + 4) = (uint16_t)(r - 1);
+    *size_out = 6u + r * (W + bl) + tail;
+  }
+  GMEM uint8_t* vals = dst + 6;
+  GMEM uint8_t* lens = vals + r * W;
+  if (lane < tail) lens[r * bl + lane] = src[m * W + lane];
+
+  // ---- every head was kept: run k is lane k's, its length the distance to the next head ------
+  if (r <= kCap) {
+    lds_order();
+    for (uint32_t k = lane; k < r; k += kWave) {
+      const uint32_t at = sh.pos[k], next = k + 1u < r ? (uint32_t)sh.pos[k + 1u] : m;
+      store_value<W>(vals + k * W, sh.value(k));
+      store_length(lens + k * bl, next - at - 1u, bl);
+    }
+    return;
+  }
+
+  // ---- pass two: head k writes values[k] and, from the head before it, lengths[k - 1] --------
+  HeadScan<W> hs(src, L, m);
+  uint32_t done = 0;
+  for (uint32_t c0 = 0; c0 < nch; c0 += kWave) {
+    const uint32_t c = c0 + lane;
+    if (!hs.step(c)) continue;
+    uint32_t prev = hs.head_below(c);
+    const uint32_t cnt = (uint32_t)__popc(hs.mask);
+    const uint32_t incl = wave_incl_sum(cnt);
+    uint32_t k = done + incl - cnt;
+    done += readlane(incl, 63);
+    for (uint32_t mk = hs.mask; mk; mk &= mk - 1u) {
+      const uint32_t j = (uint32_t)__builtin_ctz(mk);
+      const uint32_t pos = c * E + j;
+      store_value<W>(vals + k * W, element<W>(hs.ch, j));
+      if (k) store_length(lens + (k - 1u) * bl, pos - prev - 1u, bl);
+      prev = pos;
+      ++k;
+    }
+  }
+  if (lane == 0) store_length(lens + (r - 1u) * bl, m - hs.last - 1u, bl);
+}
+
+struct DecShared {
+  __attribute__((aligned(16))) uint32_t vals[(1024 + 16) / 4];  // the values of a window's runs
+  uint32_t map[32];  // bit e: a run starts at element e of the window
+};
+
+__device__ __forceinline__ uint32_t load_length(const GMEM uint8_t* lens, uint32_t k, uint32_t bl) {
+  if (bl == 1) return 1u + lens[k];
+  return 1u + lens[2 * k] + ((uint32_t)lens[2 * k + 1] << 8);
+}
+
+// the W-byte value at p (any alignment) repeated over 16 bytes
+template <uint32_t W>
+__device__ __forceinline__ uint4 load_repeated(const GMEM uint8_t* p) {
+  if constexpr (W == 1) {
+    const uint32_t v = (uint32_t)*p * 0x01010101u;
+    return make_uint4(v, v, v, v);
+  } else if constexpr (W == 2) {
+    const uint32_t v = ((uint32_t)p[0] | (uint32_t)p[1] << 8) * 0x00010001u;
+    return make_uint4(v, v, v, v);
+  } else if constexpr (W == 4) {
+    const uint32_t v = ipk::load_elem<4>(p);
+    return make_uint4(v, v, v, v);
+  } else if constexpr (W == 8) {
+    const uint32_t lo = ipk::load_elem<4>(p), hi = ipk::load_elem<4>(p + 4);
+    return make_uint4(lo, hi, lo, hi);
+  } else {
+    return make_uint4(ipk::load_elem<4>(p), ipk::load_elem<4>(p + 4), ipk::load_elem<4>(p + 8),
+                      ipk::load_elem<4>(p + 12));
+  }
+}
+
+__device__ __forceinline__ uint32_t byte_of(const uint4& v, uint32_t t) {
+  return ((t < 4 ? v.x : t < 8 ? v.y : t < 12 ? v.z : v.w) >> (8 * (t & 3u))) & 0xFFu;
+}
+
+// The runs form: src holds csize >= 4 bytes, the header's tag is valid and L <= seg.  Returns
+// false, having written nothing, for a stream that must be rejected.
+template <uint32_t W>
+__device__ __forceinline__ bool decompress_runs(const GMEM uint8_t* src, uint32_t csize, uint32_t bl,
+                                                uint32_t L, GMEM uint8_t* dst, DecShared& sh) {
+  constexpr uint32_t E = 16 / W;
+  const uint32_t lane = lane_id();
+  const uint32_t m = L / W, tail = L - m * W;
+  if (csize < 6 || (bl != 1 && bl != 2)) return false;
+  const uint32_t r = 1u + src[4] + ((uint32_t)src[5] << 8);
+  if (r > m || csize != 6u + r * (W + bl) + tail) return false;
+  const GMEM uint8_t* vals = src + 6;
+  const GMEM uint8_t* lens = vals + r * W;
+
+  // ---- the run lengths must add up to m.  The true sum can reach 2^32 (W = 1, r = 65536, every
+  // length 65536) and no further, so a 32-bit sum is wrong only there, where it wraps to 0:
+  // still rejected, because m >= r >= 1.  (Partial sums are 32 bits wide everywhere.)
+  uint32_t part = 0;
+  for (uint32_t k = lane; k < r; k += kWave) part += load_length(lens, k, bl);
+  if (readlane(wave_incl_sum(part), 63) != m) return false;
+
+  // ---- expansion, one window of 64 chunks (64 * E elements) per step ---------------------------
+  // Block b of the output is its bytes [16b - a, 16b - a + 16), a = the output's misalignment:
+  // the top a bytes of chunk b - 1 and the rest of chunk b.  Lane t of a step makes chunk
+  // 64*step + t and stores that block, 16 bytes at once unless it crosses an end of the output.
+  const uint32_t a = (uint32_t)(uintptr_t)dst & 15u;
+  const uint32_t T = m * W;
+  const uint32_t nblk = (T + a + 15u) / 16u;
+  uint32_t cur = 0;                           // the run that holds the window's first element
+  uint32_t cur_end = load_length(lens, 0, bl);  // where it ends
+  uint32_t rep_run = 0;
+  uint4 rep = load_repeated<W>(vals);         // run rep_run's value over 16 bytes
+  uint4 carry = make_uint4(0, 0, 0, 0);
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kWave) {
+    const uint32_t ws = b0 * E;
+    uint4 ch = rep;
+    if (ws < m) {
+      const uint32_t we = ws + kWave * E < m ? ws + kWave * E : m;
+      if (cur_end >= we) {
+        // one run covers the window: every lane stores its value
+        if (rep_run != cur) {
+          rep = load_repeated<W>(vals + cur * W);
+          rep_run = cur;
+        }
+        ch = rep;
+      } else {
+        // mark where the runs after `cur` start, 64 runs per step, up to the window's end
+        if (lane < 32) sh.map[lane] = 0;
+        lds_order();
+        uint32_t s = cur + 1u, pos = cur_end;
+        while (pos < we) {  // (then s < r: the lengths add up to m)
+          const uint32_t k = s + lane;
+          const uint32_t v = k < r ? load_length(lens, k, bl) : 0u;
+          const uint32_t incl = wave_incl_sum(v);
+          const uint32_t start = pos + incl - v;
+          const bool in = (k < r) & (start < we);
+          if (in) atomicOr(&sh.map[(start - ws) >> 5], 1u << ((start - ws) & 31u));
+          const uint32_t n_in = (uint32_t)__popcll(ballot(in));  // >= 1: lane 0 starts at pos
+          if (n_in == 0) break;              // (so never taken: the loop ends by construction)
+          pos += readlane(incl, n_in - 1u);  // the end of the last of them
+          s += n_in;
+        }
+        // the values of runs cur .. s - 1 (at most 64 * E of them) side by side in LDS
+        const GMEM uint8_t* p = vals + cur * W;
+        const uint32_t nbytes = (s - cur) * W;
+        for (uint32_t j = lane; j < nbytes / 4u; j += kWave) sh.vals[j] = ipk::load_elem<4>(p + 4u * j);
+        if (lane < (nbytes & 3u))
+          reinterpret_cast<uint8_t*>(sh.vals)[(nbytes & ~3u) + lane] = p[(nbytes & ~3u) + lane];
+        lds_order();
+        // an element's run is `cur` plus the number of starts at or before it
+        const uint32_t bits = (sh.map[(lane * E) >> 5] >> ((lane * E) & 31u)) & ((1u << E) - 1u);
+        const uint32_t cnt = (uint32_t)__popc(bits);
+        const uint32_t base = wave_incl_sum(cnt) - cnt;
+        uint32_t idx[E];
+#pragma unroll
+        for (uint32_t j = 0; j < E; ++j) idx[j] = base + (uint32_t)__popc(bits & ((2u << j) - 1u));
+        if constexpr (W == 16) {
+          ch = *reinterpret_cast<const uint4*>(&sh.vals[idx[0] * 4]);
+        } else if constexpr (W == 8) {
+          ch = make_uint4(sh.vals[idx[0] * 2], sh.vals[idx[0] * 2 + 1], sh.vals[idx[1] * 2],
+                          sh.vals[idx[1] * 2 + 1]);
+        } else if constexpr (W == 4) {
+          ch = make_uint4(sh.vals[idx[0]], sh.vals[idx[1]], sh.vals[idx[2]], sh.vals[idx[3]]);
+        } else {
+          uint32_t w[4];
+#pragma unroll
+          for (uint32_t q = 0; q < 4; ++q) {
+            w[q] = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4 / W; ++j) {
+              uint32_t e;
+              if constexpr (W == 2) e = reinterpret_cast<const uint16_t*>(sh.vals)[idx[q * 2 + j]];
+              else e = reinterpret_cast<const uint8_t*>(sh.vals)[idx[q * 4 + j]];
+              w[q] |= e << (8 * W * j);
+            }
+          }
+          ch = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        lds_order();
+        cur = s - 1u;
+        cur_end = pos;
+      }
+      if (cur_end == we && we < m) {  // the next window starts a run
+        ++cur;
+        cur_end += load_length(lens, cur, bl);
+      }
+    }
+    const uint4 below = from_below(ch, carry);
+    carry = lane63(ch);
+    const uint4 o = window16(below, ch, 16u - a);
+    const int32_t lo = (int32_t)(16u * (b0 + lane)) - (int32_t)a;
+    if (lo >= 0 && (uint32_t)lo + 16u <= T) {
+      *reinterpret_cast<GMEM uint4*>(dst + lo) = o;
+    } else {
+#pragma unroll
+      for (uint32_t t = 0; t < 16; ++t) {
+        const int32_t at = lo + (int32_t)t;
+        if (at >= 0 && (uint32_t)at < T) dst[at] = (uint8_t)byte_of(o, t);
+      }
+    }
+  }
+  if (lane < tail) dst[T + lane] = lens[r * bl + lane];
+  return true;
+}
+
+}  // namespace rpk
+
+// Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
+// or dsts[i]); sizes[i] = the stream's size (at most 4 + the segment's length: never a failure).
+// Nothing at or past that size is written in the slot.
+template <uint32_t W>
+__global__ __launch_bounds__(64) void runpack_compress_kernel(
+    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
+    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
+  __shared__ rpk::EncShared<W> sh;
+  const uint32_t i = blockIdx.x;
+  const uint64_t seg_off = (uint64_t)i * seg;
+  if (seg_off >= n_total) return;
+  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
+  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
+  rpk::compress_segment<W>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
+}
+
+#define BITAR_RUNPACK_INSTANCE(W)                                                              \
+  template __global__ void runpack_compress_kernel<W>(const uint8_t*, uint64_t, uint32_t,      \
+                                                      uint8_t*, uint64_t, uint8_t* const*,     \
+                                                      uint32_t*)
+BITAR_RUNPACK_INSTANCE(1);
+BITAR_RUNPACK_INSTANCE(2);
+BITAR_RUNPACK_INSTANCE(4);
+BITAR_RUNPACK_INSTANCE(8);
+BITAR_RUNPACK_INSTANCE(16);
+#undef BITAR_RUNPACK_INSTANCE
+
+// Segment i: csizes[i] bytes at srcs[i] (or slab + i*slot_stride) -> out + i*seg; produced[i] =
+// its length, or BITAR_HIP_SEGMENT_ERROR (and bit 0 of the error word) for a stream the format
+// rejects: such a segment's output range is left untouched.  The element width comes from the
+// stream's tag.  Nothing outside the stream's csizes[i] bytes is used (an aligned dword is loaded
+// only when one of its bytes is), and nothing outside the segment's first L bytes is written.
+__global__ __launch_bounds__(64) void runpack_decompress_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
+  __shared__ rpk::DecShared sh;
+  const uint32_t i = blockIdx.x;
+  if (i >= nseg) return;
+  const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
+  GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
+  const uint32_t csize = csizes[i];
+  bool ok = csize >= 4;
+  uint32_t L = 0;
+  if (ok) {
+    const uint32_t tag = src[0], bl = src[1];
+    const uint32_t lg = tag & 7u;
+    L = 1u + src[2] + ((uint32_t)src[3] << 8);
+    ok = (tag >> 4) == 7u && lg <= 4u && L <= seg;
+    if (ok && (tag & 8u)) {
+      ok = bl == 0 && csize == 4u + L;
+      if (ok) wave_copy_global(dst, src + 4, L);
+    } else if (ok) {
+      switch (lg) {
+        case 0: ok = rpk::decompress_runs<1>(src, csize, bl, L, dst, sh); break;
+        case 1: ok = rpk::decompress_runs<2>(src, csize, bl, L, dst, sh); break;
+        case 2: ok = rpk::decompress_runs<4>(src, csize, bl, L, dst, sh); break;
+        case 3: ok = rpk::decompress_runs<8>(src, csize, bl, L, dst, sh); break;
+        default: ok = rpk::decompress_runs<16>(src, csize, bl, L, dst, sh); break;
+      }
+    }
+  }
+  if (lane_id() == 0) {
+    if (ok) {
+      produced[i] = L;
+    } else {
+      produced[i] = BITAR_HIP_SEGMENT_ERROR;
+      atomicOr(err, 1u);
+    }
+  }
+}
+
+}  // namespace bitar_hip

@@ -113,6 +113,12 @@ __global__ void dictpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uin
 __global__ void dictpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                            const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                            uint32_t*);
+template <uint32_t W>
+__global__ void runpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
+                                        uint8_t* const*, uint32_t*);
+__global__ void runpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
+                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
+                                          uint32_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
 __global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
                             uint8_t*);
@@ -367,9 +373,14 @@ static bool is_dictpack(uint32_t codec) {
   return codec >= BITAR_HIP_CODEC_DICTPACK32 && codec <= BITAR_HIP_CODEC_DICTPACK128;
 }
 
+// the five RUNPACK ids, 32 + log2 of the element width (1, 2, 4, 8 or 16 bytes)
+static bool is_runpack(uint32_t codec) {
+  return codec >= BITAR_HIP_CODEC_RUNPACK8 && codec <= BITAR_HIP_CODEC_RUNPACK128;
+}
+
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
   uint64_t bound;
-  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec))
+  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec) || is_runpack(codec))
     bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
@@ -400,7 +411,12 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
     case BITAR_HIP_CODEC_FLTPACK64:
     case BITAR_HIP_CODEC_DICTPACK32:
     case BITAR_HIP_CODEC_DICTPACK64:
-    case BITAR_HIP_CODEC_DICTPACK128: return 0;  // "none": the codec has no matches at all
+    case BITAR_HIP_CODEC_DICTPACK128:
+    case BITAR_HIP_CODEC_RUNPACK8:
+    case BITAR_HIP_CODEC_RUNPACK16:
+    case BITAR_HIP_CODEC_RUNPACK32:
+    case BITAR_HIP_CODEC_RUNPACK64:
+    case BITAR_HIP_CODEC_RUNPACK128: return 0;  // "none": the codec has no matches at all
     default: return 0;                          // "unknown": no such codec
   }
 }
@@ -537,7 +553,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
       codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec) && !is_fltpack(codec) &&
-      !is_dictpack(codec))
+      !is_dictpack(codec) && !is_runpack(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -590,6 +606,20 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
     else if (codec == BITAR_HIP_CODEC_DICTPACK64) BITAR_DICTPACK(8);
     else BITAR_DICTPACK(16);
 #undef BITAR_DICTPACK
+  }
+  else if (is_runpack(codec)) {
+    // likewise (runpack.hip)
+#define BITAR_RUNPACK(W)                                                                      \
+  hipLaunchKernelGGL(bitar_hip::runpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, \
+                     s, in, n, seg, slab, slot_stride, dsts, d_sizes)
+    switch (codec) {
+      case BITAR_HIP_CODEC_RUNPACK8: BITAR_RUNPACK(1); break;
+      case BITAR_HIP_CODEC_RUNPACK16: BITAR_RUNPACK(2); break;
+      case BITAR_HIP_CODEC_RUNPACK32: BITAR_RUNPACK(4); break;
+      case BITAR_HIP_CODEC_RUNPACK64: BITAR_RUNPACK(8); break;
+      default: BITAR_RUNPACK(16); break;
+    }
+#undef BITAR_RUNPACK
   }
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
     SegOrder ord;
@@ -950,8 +980,9 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   if (is_intpack(codec)) codec = BITAR_HIP_CODEC_INTPACK8;  // (the width is in each stream's tag)
   if (is_fltpack(codec)) codec = BITAR_HIP_CODEC_FLTPACK32;  // (likewise)
   if (is_dictpack(codec)) codec = BITAR_HIP_CODEC_DICTPACK32;  // (likewise)
+  if (is_runpack(codec)) codec = BITAR_HIP_CODEC_RUNPACK8;  // (likewise)
   if (codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
-      codec != BITAR_HIP_CODEC_DICTPACK32 &&
+      codec != BITAR_HIP_CODEC_DICTPACK32 && codec != BITAR_HIP_CODEC_RUNPACK8 &&
       codec != BITAR_HIP_CODEC_LZ4 &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
@@ -983,6 +1014,10 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   }
   else if (codec == BITAR_HIP_CODEC_DICTPACK32) {
     hipLaunchKernelGGL(bitar_hip::dictpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
+                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
+  }
+  else if (codec == BITAR_HIP_CODEC_RUNPACK8) {
+    hipLaunchKernelGGL(bitar_hip::runpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
                        slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
   }
   else if (codec == BITAR_HIP_CODEC_LZ4)

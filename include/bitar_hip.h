@@ -140,7 +140,37 @@ enum bitar_hip_codec {
    * duplicate dictionary entries are accepted. */
   BITAR_HIP_CODEC_DICTPACK32 = 26,
   BITAR_HIP_CODEC_DICTPACK64 = 27,
-  BITAR_HIP_CODEC_DICTPACK128 = 28
+  BITAR_HIP_CODEC_DICTPACK128 = 28,
+  /* RUNPACK: per-segment run-length coding, for sorted or clustered columns
+   * whose values come in long runs (partition and dimension keys, coarse timestamps, status and
+   * flag bytes, byte-per-value validity).  The id is 32 + log2(w) for w = 1, 2, 4, 8 or 16
+   * bytes; no reference counterpart and no stock library reads the format.  One stream per
+   * segment of L bytes, m = L / w elements compared as byte patterns (+0.0, -0.0 and every NaN
+   * payload are distinct values), the last L - m*w bytes are the tail:
+   *   byte 0      0x70 | mode << 3 | log2(w)    mode 0 runs, 1 stored
+   *   byte 1      bl, bytes per run length: 1 or 2 (0 in the stored form)
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                           size = 4 + L
+   *   runs:       LE16(r - 1)  r = number of runs, 1 <= r <= m
+   *               values[r]    each run's element, w bytes, in order
+   *               lengths[r]   (run length - 1), bl bytes each, little-endian
+   *               tail
+   *   size = 6 + r*(w + bl) + (L - m*w)
+   * The encoder's runs are maximal (neighbouring runs have different values), bl is 1 when every
+   * run is at most 256 elements long and 2 otherwise, and the runs form is taken when its size
+   * is strictly below 4 + L; every other segment is stored (m = 0 included, and a tie, which
+   * does occur: w = 1, m = 4, r = 1 is 8 bytes either way).  The decoder takes w from the tag
+   * (all five ids select it) and rejects, before it writes anything: a high nibble other than
+   * 7, log2(w) above 4, stored with byte 1 != 0, runs with byte 1 not 1 or 2, L > seg, a runs
+   * stream shorter than 6 bytes, r > m, a stream whose size is not exactly the formula (4 + L
+   * when stored), run lengths that do not add up to exactly m.  A rejected segment's output
+   * range is left untouched.  Streams no encoder writes decode: equal neighbouring values,
+   * bl = 2 where 1 would do, a runs form larger than 4 + L. */
+  BITAR_HIP_CODEC_RUNPACK8 = 32,
+  BITAR_HIP_CODEC_RUNPACK16 = 33,
+  BITAR_HIP_CODEC_RUNPACK32 = 34,
+  BITAR_HIP_CODEC_RUNPACK64 = 35,
+  BITAR_HIP_CODEC_RUNPACK128 = 36
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -156,6 +186,12 @@ enum bitar_hip_codec {
 #define BITAR_HIP_CODEC_DICTPACK(width) \
   ((width) == 4 ? BITAR_HIP_CODEC_DICTPACK32 : (width) == 8 ? BITAR_HIP_CODEC_DICTPACK64 : \
    BITAR_HIP_CODEC_DICTPACK128)
+
+/* The RUNPACK id of an element width of 1, 2, 4, 8 or 16 bytes. */
+#define BITAR_HIP_CODEC_RUNPACK(width) \
+  ((width) == 1 ? BITAR_HIP_CODEC_RUNPACK8 : (width) == 2 ? BITAR_HIP_CODEC_RUNPACK16 : \
+   (width) == 4 ? BITAR_HIP_CODEC_RUNPACK32 : (width) == 8 ? BITAR_HIP_CODEC_RUNPACK64 : \
+   BITAR_HIP_CODEC_RUNPACK128)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -208,14 +244,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK and DICTPACK, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK and RUNPACK, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK and DICTPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK and RUNPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
@@ -409,7 +445,7 @@ int bitar_hip_filter_invert(bitar_hip_ctx* ctx, void* stream, uint32_t filter, u
                             uint32_t nseg, void* d_out);
 
 /* ---- one gzip member (RFC 1952) from DEFLATE segments ----
- * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK, FLTPACK and DICTPACK
+ * bitar_hip_compress for BITAR_HIP_CODEC_DEFLATE / _DEFLATE_DYNAMIC (any other codec, INTPACK, FLTPACK, DICTPACK and RUNPACK
  * included: BITAR_HIP_INVALID) that also stores each segment's exact bit length: d_bits[i] = the bits of
  * a coded segment up to and including its end-of-block code, 8 * d_sizes[i] for a stored
  * segment, BITAR_HIP_SEGMENT_ERROR for a failed one.  d_bits NULL: exactly
