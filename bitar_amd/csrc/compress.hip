@@ -412,7 +412,7 @@ struct Lz4Out : ByteOutT<kLz4Obuf> {
 
   // between windows: flush the records once the next window could overfill the list
   __device__ __forceinline__ void between(const GMEM uint8_t* in, const InRing& I) {
-    if (nseq > kSeqCap - 16) flush_seqs(in, I);
+    if (BITAR_RARE(nseq > kSeqCap - 16)) flush_seqs(in, I);
   }
   // One window: its matches appended as records (<= 16: matches are >= 4 bytes)
   __device__ __forceinline__ void window(const GMEM uint8_t*, const InRing&, const Window& W,
@@ -622,7 +622,7 @@ struct DflOut {
   // the tail literals start at the last match's end (after whatever is pending)
   __device__ __forceinline__ uint32_t pending_from(uint32_t anchor, uint32_t) const { return anchor; }
   __device__ __forceinline__ void between(const GMEM uint8_t* in, const InRing& I) {
-    if (npend > kSeqCap - 16) flush_seqs(in, I);
+    if (BITAR_RARE(npend > kSeqCap - 16)) flush_seqs(in, I);
   }
   // the tail literals (matches end >= 5 bytes before the segment end, so this always runs)
   __device__ __forceinline__ void sequence(const GMEM uint8_t* in, const InRing& I, uint32_t s,
@@ -704,7 +704,10 @@ __global__ __launch_bounds__(64) BITAR_LZ4C_ATTR void lz4_compress_kernel(
 #ifndef BITAR_CMP_LZ4_SKIP
 #define BITAR_CMP_LZ4_SKIP 1  // tuning knob: 0 = the plain window scan (not the oracle's LZ4 parse)
 #endif
-  parse<Lz4Out, false, BITAR_CMP_LZ4_SKIP != 0, RING, HLOG>(global_ptr(input + seg_off), n,
+#ifndef BITAR_CMP_CHAIN_LZ4
+#define BITAR_CMP_CHAIN_LZ4 BITAR_CMP_CHAIN  // the LZ4 instantiations' chain form (window_parse.hip.h)
+#endif
+  parse<Lz4Out, false, BITAR_CMP_LZ4_SKIP != 0, RING, HLOG, BITAR_CMP_CHAIN_LZ4>(global_ptr(input + seg_off), n,
                                          global_ptr(input + n_total), table, inring,
                                          RING - 1536u, 0xFFFFFFFFu, o);
   o.flush(o.op, true);

@@ -238,21 +238,36 @@ constexpr uint32_t kNextStop = 128;
 
 // The list path's token walk: from lane 0 (eligible: the caller's test), set every chain
 // lane in `chain`; one v_readlane (the word read is the next lane select), one s_bitset1,
-// one compare and one branch per sequence, unrolled twice.  A VALU-written SGPR needs 4
+// one compare and one branch per sequence.  A VALU-written SGPR needs 4
 // wait states before it is a lane select: s_nop 0, the compare, the branch and the bitset.
 // Returns the word that ended the walk (> 63).
+// BITAR_LZ4D_WALK_UNROLL links per trip (2, 4, 8 or 16): a wave waits for its instruction
+// stream after every taken branch, and a kind-1 window's chain is ~12 sequences long (decode
+// kind 1 1.48 -> 1.45 ms/GiB with 16 against 2).
+#ifndef BITAR_LZ4D_WALK_UNROLL
+#define BITAR_LZ4D_WALK_UNROLL 16
+#endif
+#define BITAR_WC_LINK                       \
+  "s_bitset1_b64 %[ch], %[l]\n"             \
+  "v_readlane_b32 %[l], %[nx], %[l]\n"      \
+  "s_nop 0\n"
+#define BITAR_WC_STEP BITAR_WC_LINK "s_cmp_gt_u32 %[l], 63\n" "s_cbranch_scc1 L_wo_%=\n"
+#define BITAR_WC_STEP4 BITAR_WC_STEP BITAR_WC_STEP BITAR_WC_STEP BITAR_WC_STEP
+#if BITAR_LZ4D_WALK_UNROLL == 16
+#define BITAR_WC_STEPS BITAR_WC_STEP4 BITAR_WC_STEP4 BITAR_WC_STEP4 BITAR_WC_STEP BITAR_WC_STEP BITAR_WC_STEP
+#elif BITAR_LZ4D_WALK_UNROLL == 8
+#define BITAR_WC_STEPS BITAR_WC_STEP4 BITAR_WC_STEP BITAR_WC_STEP BITAR_WC_STEP
+#elif BITAR_LZ4D_WALK_UNROLL == 4
+#define BITAR_WC_STEPS BITAR_WC_STEP BITAR_WC_STEP BITAR_WC_STEP
+#else
+#define BITAR_WC_STEPS BITAR_WC_STEP
+#endif
 __device__ __forceinline__ uint32_t walk_chain(uint32_t nx, uint64_t& chain) {
   uint32_t l = 0;
   __asm__ volatile(
       "L_wc_%=:\n"
-      "s_bitset1_b64 %[ch], %[l]\n"
-      "v_readlane_b32 %[l], %[nx], %[l]\n"
-      "s_nop 0\n"
-      "s_cmp_gt_u32 %[l], 63\n"
-      "s_cbranch_scc1 L_wo_%=\n"
-      "s_bitset1_b64 %[ch], %[l]\n"
-      "v_readlane_b32 %[l], %[nx], %[l]\n"
-      "s_nop 0\n"
+      BITAR_WC_STEPS
+      BITAR_WC_LINK
       "s_cmp_lt_u32 %[l], 64\n"
       "s_cbranch_scc1 L_wc_%=\n"
       "L_wo_%=:\n"
@@ -542,7 +557,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
         uint32_t more = 0;
         if (s.ip + kBatchIn <= s.csize) {
           uint32_t wrel = src_lo + s.ip - (uint32_t)s.wb;  // window index of ip (mod 2^32)
-          if (wrel > kWin - kBatchIn) {  // (the list is empty here: a flush came before)
+          if (BITAR_RARE(wrel > kWin - kBatchIn)) {  // (the list is empty here: a flush came before)
             win_at(s, win, s.ip, kBatchIn);
             wrel = src_lo + s.ip - (uint32_t)s.wb;
           }
@@ -569,7 +584,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
             const bool cfar = (colen <= kSeqOut) & (coff - 1u < s.op + cL);
             const bool celig = cfar & (coff <= kNearOff) & (lane < kWave - 1);
             const uint64_t E = ballot(celig);
-            if (!(E & 1ull)) {
+            if (BITAR_RARE(!(E & 1ull))) {
               // the first token is not eligible; if it would be with far history, defer the
               // segment
               want_far = (ballot(cfar) & 1ull) != 0;
@@ -625,7 +640,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
             }
           } while (t >= kBatchIn);
         }
-        if (want_far) break;
+        if (BITAR_RARE(want_far)) break;
         if (nseq) {
           // (4) flush.  Positions are relative to the output position at the flush (q: this
           // lane's byte, R: the step's first); per record: os = its first byte, rM = its
@@ -634,7 +649,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
           const uint32_t len = live ? lw0 >> 24 : 0u;
           const uint32_t incl = wave_incl_sum(len);
           const uint32_t total = readlane(incl, kWave - 1);
-          if (total > s.cap - s.op) { ok = false; break; }  // (op <= cap always)
+          if (BITAR_RARE(total > s.cap - s.op)) { ok = false; break; }  // (op <= cap always)
           if constexpr (BITAR_LZ4D_ENDRULES == 1 || BITAR_LZ4D_ENDRULES == 2) {
             const uint32_t lastw = readlane(lw0, nseq - 1);  // the last match's length
             last_ml = (lastw >> 24) - ((lastw >> 16) & 0xFFu);
@@ -748,7 +763,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
             }
           };
           for (uint32_t R = 0; R < total; R += 2 * kWave) {
-            if (s.op + 2 * kWave - s.flushed > kFlushAt) flush(s, ring, s.op, false);
+            if (BITAR_RARE(s.op + 2 * kWave - s.flushed > kFlushAt)) flush(s, ring, s.op, false);
             const uint32_t left = total - R;
             if (left > kWave) round(std::integral_constant<uint32_t, 2>{}, R);
             else round(std::integral_constant<uint32_t, 1>{}, R);

@@ -16,7 +16,8 @@
 //      wins a slot: the hardware keeps the highest lane's write, see BITAR_CMP_NOREDO);
 //   2. lanes with a candidate verify + measure the match on 16 bytes from the ring, and
 //      lanes still matching extend in parallel up to 32 bytes;
-//   3. a scalar chain walk picks the greedy matches in lane order (one ctz per match,
+//   3. a scalar chain walk picks the greedy matches in lane order (every lane's successor is
+//      computed on the VALU, the walk is one v_readlane per match, 8 matches per trip;
 //      cooperative extension only for matches reaching 32 bytes);
 //   4. the codec's emitter (E::window) writes the window's output lane-parallel (or, the LZ4
 //      emitter, records the matches and writes batches of them in E::between).
@@ -72,6 +73,9 @@ constexpr uint32_t kRow = 1024;                   // prefetch row: one 16-B bloc
 #define BITAR_CMP_PREEXT 32
 #endif
 constexpr uint32_t kPreExt = BITAR_CMP_PREEXT;    // parallel per-lane match extension limit
+// The parse loop's rare branches (the row load, the emitter's flush, skipped windows and probes,
+// the segment's last windows, the cooperative extension) are marked BITAR_RARE (wave.hip.h), so
+// that the common window's path is laid out to fall through.
 
 template <uint32_t HLOG = kHashLog>
 __device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - HLOG); }
@@ -315,22 +319,44 @@ __device__ __forceinline__ uint32_t chain_fast2(uint64_t& m, uint32_t lenw, uint
 // the VALU -- nx[j] = the first valid lane at or past j + len[j] (64..127: the chain leaves
 // the window; 128 + j: lane j needs the cooperative extension, whose length is not known yet) --
 // so the scalar loop per match is one v_readlane (the next lane is the next lane select),
-// one s_bitset1, one compare and one branch (unrolled twice).  Matches per window: 6.6 on
+// one s_bitset1, one compare and one branch.  Matches per window: 6.6 on
 // kind 1, up to 8.6 on kind 5 (oracle counts), so the chain was ~half of the parse's scalar
 // instructions.  Returns the lane that stopped the walk (64..127, or 128 + an extension lane),
 // every chain lane before it set in `chain`.  (A VALU-written SGPR needs 4 wait states before
 // it is a lane select: s_nop 1 + the compare + the branch + the bitset.)
+// BITAR_CMP_CHAIN_UNROLL: links per trip of the loop (2, 4, 8 or 16).  A wave waits for its
+// instruction stream after every taken branch, and the walk is the window's longest dependent
+// chain: 8 links per trip leave the usual window one taken branch, the walk's exit (kind-1 LZ4
+// compress 2.44 -> 2.41 ms/GiB against 2; 16 measured the same as 8).
+// BITAR_CMP_CHAIN_NOP: the s_nop's operand (0: exactly the 4 wait states; measured level).
+#ifndef BITAR_CMP_CHAIN_UNROLL
+#define BITAR_CMP_CHAIN_UNROLL 8
+#endif
+#ifndef BITAR_CMP_CHAIN_NOP
+#define BITAR_CMP_CHAIN_NOP 1
+#endif
+#define BITAR_CS_STR2(x) #x
+#define BITAR_CS_STR(x) BITAR_CS_STR2(x)
+#define BITAR_CS_LINK                        \
+  "s_bitset1_b64 %[ch], %[l]\n"              \
+  "v_readlane_b32 %[l], %[nx], %[l]\n"       \
+  "s_nop " BITAR_CS_STR(BITAR_CMP_CHAIN_NOP) "\n"
+#define BITAR_CS_STEP BITAR_CS_LINK "s_cmp_gt_u32 %[l], 63\n" "s_cbranch_scc1 L_co_%=\n"
+#define BITAR_CS_STEP4 BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP
+#if BITAR_CMP_CHAIN_UNROLL == 16
+#define BITAR_CS_STEPS BITAR_CS_STEP4 BITAR_CS_STEP4 BITAR_CS_STEP4 BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP
+#elif BITAR_CMP_CHAIN_UNROLL == 8
+#define BITAR_CS_STEPS BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP
+#elif BITAR_CMP_CHAIN_UNROLL == 4
+#define BITAR_CS_STEPS BITAR_CS_STEP BITAR_CS_STEP BITAR_CS_STEP
+#else
+#define BITAR_CS_STEPS BITAR_CS_STEP
+#endif
 __device__ __forceinline__ uint32_t chain_succ(uint32_t l, uint32_t nx, uint64_t& chain) {
   __asm__ volatile(
       "L_cs_%=:\n"
-      "s_bitset1_b64 %[ch], %[l]\n"
-      "v_readlane_b32 %[l], %[nx], %[l]\n"
-      "s_nop 1\n"
-      "s_cmp_gt_u32 %[l], 63\n"
-      "s_cbranch_scc1 L_co_%=\n"
-      "s_bitset1_b64 %[ch], %[l]\n"
-      "v_readlane_b32 %[l], %[nx], %[l]\n"
-      "s_nop 1\n"
+      BITAR_CS_STEPS
+      BITAR_CS_LINK
       "s_cmp_lt_u32 %[l], 64\n"
       "s_cbranch_scc1 L_cs_%=\n"
       "L_co_%=:\n"
@@ -338,6 +364,80 @@ __device__ __forceinline__ uint32_t chain_succ(uint32_t l, uint32_t nx, uint64_t
       : [nx] "v"(nx)
       : "scc");
   return l;
+}
+// Form 4 (BITAR_CMP_CHAIN == 4; built for comparison, 20 % slower on kind 1: its 9 dependent
+// ds_bpermute and 26 VALU cost more than the walk they replace): no walk.  Every
+// lane holds the set of lanes reachable from
+// it as a 64-bit mask (r_lo, r_hi), found by pointer doubling on the jump pointer j = nx
+// (lanes whose successor is not in the window -- nx >= 64 -- point at themselves): per round
+// r |= r[j] (two ds_bpermute), j = j[j] (one).  After k rounds r holds the lane and its next
+// 2^k - 1 successors; a window has at most 16 matches of >= 4 bytes, so 4 rounds.  The first
+// round's r[j] is the bit of j itself (BITAR_CMP_CHAIN_R1 == 1: made on the VALU instead of
+// read through the LDS pipe).  The chain from lane l is then two v_readlane.
+#ifndef BITAR_CMP_CHAIN_R1
+#define BITAR_CMP_CHAIN_R1 1
+#endif
+__device__ __forceinline__ void lane_bit(uint32_t l, uint32_t& lo, uint32_t& hi) {
+  const uint32_t b = 1u << (l & 31u);
+  lo = l < 32u ? b : 0u;
+  hi = l < 32u ? 0u : b;
+}
+__device__ __forceinline__ void chain_reach(uint32_t nx, uint32_t& r_lo, uint32_t& r_hi) {
+  const uint32_t lane = lane_id();
+  const uint32_t j = nx < (uint32_t)kWave ? nx : lane;
+  uint32_t j4 = j << 2;  // (ds_bpermute takes a byte address)
+  lane_bit(lane, r_lo, r_hi);
+#pragma unroll
+  for (uint32_t r = 0; r < 4; ++r) {
+    uint32_t a, b;
+    if (r == 0 && BITAR_CMP_CHAIN_R1) {
+      lane_bit(j, a, b);
+    } else {
+      a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)j4, (int)r_lo);
+      b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)j4, (int)r_hi);
+    }
+    if (r < 3) j4 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)j4, (int)j4);
+    r_lo |= a;
+    r_hi |= b;
+  }
+}
+// the chain from lane l into `chain`; returns what chain_succ returns: nx of the last chain lane
+__device__ __forceinline__ uint32_t chain_take(uint32_t l, uint32_t nx, uint32_t r_lo,
+                                               uint32_t r_hi, uint64_t& chain) {
+  chain |= (uint64_t)readlane(r_lo, l) | (uint64_t)readlane(r_hi, l) << 32;
+  return readlane(nx, highbit(chain));
+}
+
+// Form 5 (BITAR_CMP_CHAIN == 5; built for comparison, 3.5 % slower on kind 1: the ds_bpermute
+// stands between the match lengths and the walk): form 3's walk, two links per scalar step.
+// s1 = min(nx, 63)
+// (lane 63 is its own successor there: a valid lane 63 has nx >= 67, an invalid one nx = 64),
+// s2 = s1[s1] by one ds_bpermute; per step two v_readlane through one lane select, two
+// s_bitset1, one compare, one branch.  The walk stops on reaching 63, which stands for "left
+// the window", "extension lane" and lane 63 alike: bit 63 is cleared afterwards and the last
+// chain lane's nx says which it was.
+__device__ __forceinline__ uint32_t chain_succ2(uint32_t l0, uint32_t nx, uint32_t s1, uint32_t s2,
+                                                uint64_t& chain) {
+  uint32_t l = l0, a;
+  __asm__ volatile(
+      "L_c5_%=:\n"
+      "s_bitset1_b64 %[ch], %[l]\n"
+      "v_readlane_b32 %[a], %[s1], %[l]\n"
+      "v_readlane_b32 %[l], %[s2], %[l]\n"
+      "s_bitset1_b64 %[ch], %[a]\n"
+      "s_nop 0\n"
+      "s_cmp_lt_u32 %[l], 63\n"
+      "s_cbranch_scc1 L_c5_%=\n"
+      : [l] "+s"(l), [a] "=&s"(a), [ch] "+s"(chain)
+      : [s1] "v"(s1), [s2] "v"(s2)
+      : "scc");
+  chain = (chain & ~(1ull << 63)) | 1ull << l0;
+  uint32_t r = readlane(nx, highbit(chain));
+  if (r == 63u) {  // lane 63 holds the chain's next match
+    chain |= 1ull << 63;
+    r = readlane(nx, 63u);
+  }
+  return r;
 }
 // per lane: nx as above, from e = lane + lenw (lenw = 128 on extension lanes).  f = the first
 // valid lane at or past e (64: none) is >= e whenever e < 64, so max(f, e) is f there and e
@@ -371,8 +471,9 @@ constexpr uint32_t kRepAhead = 3;
 constexpr uint32_t kSkipProbe = 128, kSkipWide = 640;
 // RING / HLOG: the input ring's size and the hash table's log2 size (the defaults: 4 KiB and
 // 1024 entries; the wide LZ4 parse: 16 KiB and 4096, max_dist = RING - 1536 either way).
+// CH: the chain form (forms 3, 4 and 5 are chosen per instantiation; 1 and 2 per build).
 template <class E, bool REP = false, bool SKIP = false, uint32_t RING = kIn,
-          uint32_t HLOG = kHashLog>
+          uint32_t HLOG = kHashLog, uint32_t CH = BITAR_CMP_CHAIN>
 __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, const GMEM uint8_t* in_end,
                                       uint16_t* table, uint8_t* inring, uint32_t max_dist,
                                       uint32_t max_mlen, E& em) {
@@ -469,7 +570,7 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
       // match_limit (and max_mlen).  Elsewhere neither binds (every lane's limit exceeds
       // kPreExt), so those checks -- 6 VALU per window -- run only here, after the
       // pre-extension (clamping its result is the same as clamping each step).
-      if (x >= x_edge) {
+      if (BITAR_RARE(x >= x_edge)) {
         __asm__ volatile("");  // (keeps this a branch: if-converted, every window paid it)
         const uint32_t l = match_limit - p;
         const uint32_t lim = act ? (l < max_mlen ? l : max_mlen) : 0u;
@@ -498,15 +599,29 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
       uint32_t mlen_v = len;
       uint64_t m = valid;
       uint32_t e = 0;
-#if BITAR_CMP_CHAIN == 3
+#if BITAR_CMP_CHAIN >= 3
+      static_assert(CH >= 3 && CH <= 5, "chain forms 1 and 2 are build-wide");
       uint32_t lenw;
       __asm__("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lenw) : "v"(len), "v"(kExtLen), "s"(extm));
       if (valid) {
         const uint32_t nx = chain_next(valid, lane + lenw);
         uint32_t l = lowbit(valid);
-        for (;;) {
-          l = chain_succ(l, nx, chain);
-          if (l < 128u) break;
+        uint32_t ca = 0, cb = 0;  // form 4: the reach mask; form 5: s1, s2
+        if constexpr (CH == 4) {
+          chain_reach(nx, ca, cb);
+        } else if constexpr (CH == 5) {
+          ca = min(nx, 63u);
+          cb = bpermute(ca, ca);
+        }
+        auto walk = [&](uint32_t from) __attribute__((always_inline)) -> uint32_t {
+          if constexpr (CH == 4) return chain_take(from, nx, ca, cb, chain);
+          else if constexpr (CH == 5) return chain_succ2(from, nx, ca, cb, chain);
+          else return chain_succ(from, nx, chain);
+        };
+        // (the first walk stands outside the extension loop, so that the common window -- no
+        // extension lane -- falls through to the emitter)
+        l = walk(l);
+        if (BITAR_RARE(l >= 128u)) for (;;) {
           l -= 128u;  // an extension lane (its chain bit is set): extend it cooperatively
           const uint32_t i = x + l;
           uint32_t li = match_limit - i;
@@ -553,7 +668,8 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
           const uint32_t ee = l + k;
           const uint64_t rest = ee < kWave ? valid & (~0ull << ee) : 0ull;
           if (!rest) break;
-          l = lowbit(rest);
+          l = walk(lowbit(rest));
+          if (l < 128u) break;
         }
         const uint32_t last = highbit(chain);
         e = last + readlane(mlen_v, last);
@@ -624,7 +740,7 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
         e = l + mlen;
         m = e < kWave ? valid & (~0ull << e) : 0ull;
       }
-#if BITAR_CMP_CHAIN == 3
+#if BITAR_CMP_CHAIN >= 3
       }
 #endif
       if (chain) pos = x + e;
@@ -696,7 +812,7 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
     uint32_t next_load = kRow / 2;
     uint32_t g = 0;  // SKIP: the gate, >= pos
     for (uint32_t x = 0; x <= last_start;) {
-      if (x >= next_load) {
+      if (BITAR_RARE(x >= next_load)) {
         const uint32_t k = next_load / kRow;
         lds_order();
         write_row(k + 1, nxt);
@@ -709,7 +825,7 @@ __device__ __forceinline__ uint32_t parse(const GMEM uint8_t* in, uint32_t n, co
       // the emitter's batched work, between windows (fewer live registers than inside one)
       em.between(in, I);
       if constexpr (SKIP) {
-        if (x - g + (kWave - 1) >= kSkipProbe + kWave - 1) {  // g >= x + 64, or x >= g + 128
+        if (BITAR_RARE(x - g + (kWave - 1) >= kSkipProbe + kWave - 1)) {  // g >= x + 64, or x >= g + 128
           if (pos >= x + kWave) {  // inside the current match
             // every window lying wholly inside it at once (skipped windows do nothing else),
             // but not past the next row load, which the loop's top must see
