@@ -26,6 +26,9 @@ CODEC_DICTPACK32, CODEC_DICTPACK64, CODEC_DICTPACK128 = 26, 27, 28
 # RUNPACK: per-segment run lengths of 1 / 2 / 4 / 8 / 16-byte elements (any id decodes)
 CODEC_RUNPACK8, CODEC_RUNPACK16, CODEC_RUNPACK32, CODEC_RUNPACK64, CODEC_RUNPACK128 = \
     32, 33, 34, 35, 36
+# AUTOPACK: per segment the smallest of the applicable four above (any id decodes all of them)
+CODEC_AUTOPACK8, CODEC_AUTOPACK16, CODEC_AUTOPACK32, CODEC_AUTOPACK64, CODEC_AUTOPACK128 = \
+    40, 41, 42, 43, 44
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -183,6 +186,15 @@ def codec_runpack(width):
                 16: CODEC_RUNPACK128}[width]
     except (KeyError, TypeError):
         raise ValueError(f"RUNPACK element width must be 1, 2, 4, 8 or 16, not {width!r}") from None
+
+
+def codec_autopack(width):
+    """the AUTOPACK codec id of an element width of 1, 2, 4, 8 or 16 bytes"""
+    try:
+        return {1: CODEC_AUTOPACK8, 2: CODEC_AUTOPACK16, 4: CODEC_AUTOPACK32, 8: CODEC_AUTOPACK64,
+                16: CODEC_AUTOPACK128}[width]
+    except (KeyError, TypeError):
+        raise ValueError(f"AUTOPACK element width must be 1, 2, 4, 8 or 16, not {width!r}") from None
 
 
 def max_distance(codec):
@@ -379,6 +391,26 @@ class Engine:
         """entry i: sizes[i] bytes from srcs[i] to dsts[i] (int64 / int32 device tensors)"""
         check(lib().bitar_hip_copy_batch(self.ctx, self._stream(stream), _ptr(srcs), _ptr(dsts),
                                          _ptr(sizes), n))
+
+    def autopack_census(self, slab, stride, sizes, nseg):
+        """what an AUTOPACK slab is made of: {"INTPACK", "FLTPACK", "DICTPACK", "RUNPACK": the
+        segments packed in that format, "stored": those in any format's stored form, "other":
+        empty streams and tags of no format}.  Reads the tag bytes only (a strided view of the
+        slab on torch's current stream); waits for them."""
+        t = self.torch
+        if nseg == 0:
+            return {k: 0 for k in ("INTPACK", "FLTPACK", "DICTPACK", "RUNPACK", "stored", "other")}
+        tags = t.as_strided(slab, (nseg,), (stride,)).to(t.int64)
+        nib = tags >> 4
+        live = sizes[:nseg] != 0
+        # INTPACK and FLTPACK store with mode 2 in bits 2..3, DICTPACK and RUNPACK with bit 3
+        stored = t.where(nib <= 5, (tags >> 2 & 3) == 2, (tags >> 3 & 1) == 1)
+        known = live & (nib >= 4) & (nib <= 7)
+        out = {name: int((known & ~stored & (nib == k)).sum())
+               for k, name in ((4, "INTPACK"), (5, "FLTPACK"), (6, "DICTPACK"), (7, "RUNPACK"))}
+        out["stored"] = int((known & stored).sum())
+        out["other"] = nseg - int(known.sum())
+        return out
 
     def sync(self, stream=None):
         s = self._stream(stream) if stream is not False else None

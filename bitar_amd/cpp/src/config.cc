@@ -14,6 +14,7 @@ std::string_view ToString(Codec c) {
     case Codec::FLTPACK: return "FLTPACK";
     case Codec::DICTPACK: return "DICTPACK";
     case Codec::RUNPACK: return "RUNPACK";
+    case Codec::AUTOPACK: return "AUTOPACK";
   }
   return "UNKNOWN";
 }

@@ -293,7 +293,7 @@ bool OnDevice(std::uint64_t address, int device) {
 
 // DEFLATE + FIXED -> fixed-Huffman blocks; DEFLATE + DYNAMIC (the reference default,
 // config.h:151) or DEFAULT (the PMD's choice) -> dynamic Huffman
-// INTPACK, FLTPACK, DICTPACK, RUNPACK -> the id of the configured element width
+// INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK -> the id of the configured element width
 template <typename Cfg>
 std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
   switch (c.codec()) {
@@ -301,6 +301,7 @@ std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
     case Codec::FLTPACK: return BITAR_HIP_CODEC_FLTPACK(element_width);
     case Codec::DICTPACK: return BITAR_HIP_CODEC_DICTPACK(element_width);
     case Codec::RUNPACK: return BITAR_HIP_CODEC_RUNPACK(element_width);
+    case Codec::AUTOPACK: return BITAR_HIP_CODEC_AUTOPACK(element_width);
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     default:
@@ -769,7 +770,7 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
       configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::INTPACK &&
       configuration_->codec() != Codec::FLTPACK && configuration_->codec() != Codec::DICTPACK &&
-      configuration_->codec() != Codec::RUNPACK)
+      configuration_->codec() != Codec::RUNPACK && configuration_->codec() != Codec::AUTOPACK)
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
   if (configuration_->max_sgl_segs() < 1) configuration_->set_max_sgl_segs(1);
@@ -818,6 +819,14 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
       return arrow::Status::Invalid("RUNPACK cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
   }
+  if (configuration_->codec() == Codec::AUTOPACK) {
+    const auto w = element_width();
+    if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
+      return arrow::Status::Invalid("element_width (", w, ") of AUTOPACK must be 1, 2, 4, 8 or 16");
+    if (configuration_->max_sgl_segs() > 1)
+      return arrow::Status::Invalid("AUTOPACK cannot be combined with chained operations "
+                                    "(max_sgl_segs > 1)");
+  }
   // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
   // other value is refused rather than ignored (the reference always sets 1)
   if (configuration_->level() < 1 || configuration_->level() > 9)
@@ -839,7 +848,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
   if (configuration_->codec() == Codec::INTPACK || configuration_->codec() == Codec::FLTPACK ||
       configuration_->codec() == Codec::DICTPACK ||
-      configuration_->codec() == Codec::RUNPACK) {  // no matches, no window: ignored, reported 0
+      configuration_->codec() == Codec::RUNPACK ||
+      configuration_->codec() == Codec::AUTOPACK) {  // no matches, no window: ignored, reported 0
     encoder_window_ = 0;
     configuration_->set_window_size(0);
   } else if (configuration_->window_size() == 0) {
@@ -902,6 +912,8 @@ arrow::Status HipCompressDevice::ValidateConfiguration() {
       return arrow::Status::Invalid("DICTPACK takes no filter");
     if (hip_configuration->codec() == Codec::RUNPACK)
       return arrow::Status::Invalid("RUNPACK takes no filter");
+    if (hip_configuration->codec() == Codec::AUTOPACK)
+      return arrow::Status::Invalid("AUTOPACK takes no filter");
   }
   return HipGfx950CompressDevice::ValidateConfiguration();
 }

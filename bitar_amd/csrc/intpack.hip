@@ -20,6 +20,7 @@
 // (Reductions, element loads and stores and the payload emitter: bitpack.hip.h, shared with
 // fltpack.hip.)
 #include "../../include/bitar_hip.h"
+#include "autopack.hip.h"
 #include "bitpack.hip.h"
 
 namespace bitar_hip {
@@ -60,7 +61,10 @@ struct Shared {
   uint32_t stage[kStageDwords];                            // one miniblock's bit string
 };
 
-template <uint32_t W>
+// STORE = false is AUTOPACK's candidate form (autopack.hip): a segment that takes the stored form
+// writes its size alone -- a later candidate's stored form is never selected, it ties with
+// RUNPACK's at best -- and every other segment is written as ever.
+template <uint32_t W, bool STORE = true>
 __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32_t L,
                                                  GMEM uint8_t* dst, uint32_t* size_out,
                                                  Shared& sh) {
@@ -113,10 +117,10 @@ __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32
   GMEM uint32_t* head = reinterpret_cast<GMEM uint32_t*>(dst);  // (slots are 16-B aligned)
   if (!(total < 4u + L)) {
     if (lane == 0) {
-      *head = 0x40u | 2u << 2 | kLog | (L - 1) << 16;
+      if constexpr (STORE) *head = 0x40u | 2u << 2 | kLog | (L - 1) << 16;
       *size_out = 4u + L;
     }
-    wave_copy_global(dst + 4, src, L);
+    if constexpr (STORE) wave_copy_global(dst + 4, src, L);
     return;
   }
   if (lane == 0) {
@@ -234,18 +238,39 @@ template __global__ void intpack_compress_kernel<4>(const uint8_t*, uint64_t, ui
 template __global__ void intpack_compress_kernel<8>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
                                                     uint64_t, uint8_t* const*, uint32_t*);
 
+// The same, for a candidate of AUTOPACK: a segment that would be stored gets its size only.
+template <uint32_t W>
+__global__ __launch_bounds__(64) void intpack_compress_candidate_kernel(
+    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
+    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
+  __shared__ ipk::Shared sh;
+  const uint32_t i = blockIdx.x;
+  const uint64_t seg_off = (uint64_t)i * seg;
+  if (seg_off >= n_total) return;
+  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
+  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
+  ipk::compress_segment<W, false>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
+}
+
+template __global__ void intpack_compress_candidate_kernel<1>(const uint8_t*, uint64_t, uint32_t,
+    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_candidate_kernel<2>(const uint8_t*, uint64_t, uint32_t,
+    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_candidate_kernel<4>(const uint8_t*, uint64_t, uint32_t,
+    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
+template __global__ void intpack_compress_candidate_kernel<8>(const uint8_t*, uint64_t, uint32_t,
+    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
+
 // Segment i: csizes[i] bytes at srcs[i] (or slab + i*slot_stride) -> out + i*seg; produced[i] =
 // its length, or BITAR_HIP_SEGMENT_ERROR (and bit 0 of the error word) for a stream the format
 // rejects.  The element width comes from the stream's tag.  Nothing outside the stream's
 // csizes[i] bytes is used (an aligned dword is loaded only when one of its bytes is), and
 // nothing outside the segment's seg bytes is written.
-__global__ __launch_bounds__(64) void intpack_decompress_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
-  __shared__ ipk::DecShared sh;
-  const uint32_t i = blockIdx.x;
-  if (i >= nseg) return;
+__device__ __forceinline__ void intpack_decompress_segment(
+    uint32_t i, const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab,
+    uint64_t slot_stride, const uint32_t* __restrict__ csizes, uint32_t seg,
+    uint8_t* __restrict__ out, uint32_t* __restrict__ produced, uint32_t* __restrict__ err,
+    ipk::DecShared& sh) {
   const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
   GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
   const uint32_t csize = csizes[i];
@@ -276,6 +301,30 @@ __global__ __launch_bounds__(64) void intpack_decompress_kernel(
       atomicOr(err, 1u);
     }
   }
+}
+
+__global__ __launch_bounds__(64) void intpack_decompress_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
+  __shared__ ipk::DecShared sh;
+  const uint32_t i = blockIdx.x;
+  if (i >= nseg) return;
+  intpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
+}
+
+// AUTOPACK's decoder of this format (autopack.hip.h): a grid of nseg workgroups of which the
+// listed ones -- or, without a list, those whose stream carries this format's tag -- do exactly
+// what the kernel above does for their segment; the others leave at once and write nothing.
+__global__ __launch_bounds__(64) void intpack_decompress_listed_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err, const uint32_t* __restrict__ list,
+    const uint32_t* __restrict__ count) {
+  __shared__ ipk::DecShared sh;
+  const uint32_t i = listed_segment(4u, list, count, srcs, slab, slot_stride, csizes, nseg);
+  if (i == kNoSegment) return;
+  intpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
 }
 
 }  // namespace bitar_hip

@@ -23,6 +23,7 @@
 // decoder builds chunks from the runs and stores them as 16-byte blocks aligned in the OUTPUT,
 // whatever the alignment of the segment.
 #include "../../include/bitar_hip.h"
+#include "autopack.hip.h"
 #include "bitpack.hip.h"
 
 namespace bitar_hip {
@@ -529,13 +530,11 @@ BITAR_RUNPACK_INSTANCE(16);
 // rejects: such a segment's output range is left untouched.  The element width comes from the
 // stream's tag.  Nothing outside the stream's csizes[i] bytes is used (an aligned dword is loaded
 // only when one of its bytes is), and nothing outside the segment's first L bytes is written.
-__global__ __launch_bounds__(64) void runpack_decompress_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
-  __shared__ rpk::DecShared sh;
-  const uint32_t i = blockIdx.x;
-  if (i >= nseg) return;
+__device__ __forceinline__ void runpack_decompress_segment(
+    uint32_t i, const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab,
+    uint64_t slot_stride, const uint32_t* __restrict__ csizes, uint32_t seg,
+    uint8_t* __restrict__ out, uint32_t* __restrict__ produced, uint32_t* __restrict__ err,
+    rpk::DecShared& sh) {
   const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
   GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
   const uint32_t csize = csizes[i];
@@ -567,6 +566,30 @@ __global__ __launch_bounds__(64) void runpack_decompress_kernel(
       atomicOr(err, 1u);
     }
   }
+}
+
+__global__ __launch_bounds__(64) void runpack_decompress_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
+  __shared__ rpk::DecShared sh;
+  const uint32_t i = blockIdx.x;
+  if (i >= nseg) return;
+  runpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
+}
+
+// AUTOPACK's decoder of this format (autopack.hip.h): a grid of nseg workgroups of which the
+// listed ones -- or, without a list, those whose stream carries this format's tag -- do exactly
+// what the kernel above does for their segment; the others leave at once and write nothing.
+__global__ __launch_bounds__(64) void runpack_decompress_listed_kernel(
+    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
+    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
+    uint32_t* __restrict__ produced, uint32_t* __restrict__ err, const uint32_t* __restrict__ list,
+    const uint32_t* __restrict__ count) {
+  __shared__ rpk::DecShared sh;
+  const uint32_t i = listed_segment(7u, list, count, srcs, slab, slot_stride, csizes, nseg);
+  if (i == kNoSegment) return;
+  runpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
 }
 
 }  // namespace bitar_hip

@@ -119,6 +119,28 @@ __global__ void runpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint
 __global__ void runpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                           const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                           uint32_t*);
+template <uint32_t W>
+__global__ void intpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                  uint64_t, uint8_t* const*, uint32_t*);
+template <uint32_t W>
+__global__ void fltpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                  uint64_t, uint8_t* const*, uint32_t*);
+template <uint32_t W>
+__global__ void dictpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
+                                                   uint64_t, uint8_t* const*, uint32_t*);
+#define BITAR_LISTED_DECODER(name)                                                           \
+  __global__ void name(const uint8_t* const*, const uint8_t*, uint64_t, const uint32_t*, uint32_t, \
+                       uint32_t, uint8_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*)
+BITAR_LISTED_DECODER(intpack_decompress_listed_kernel);
+BITAR_LISTED_DECODER(fltpack_decompress_listed_kernel);
+BITAR_LISTED_DECODER(dictpack_decompress_listed_kernel);
+BITAR_LISTED_DECODER(runpack_decompress_listed_kernel);
+#undef BITAR_LISTED_DECODER
+__global__ void autopack_select_kernel(const uint8_t*, uint64_t, const uint32_t*, uint32_t, uint32_t,
+                                       uint32_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
+__global__ void autopack_route_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
+                                      const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*,
+                                      uint32_t*);
 __global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
 __global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
                             uint8_t*);
@@ -211,8 +233,8 @@ constexpr uint32_t kMaxZstdFrame = 1u << 30;
 constexpr uint64_t kChunkSegs = 32768;
 struct Chunks {
   uint64_t size;
-  explicit Chunks(uint64_t nseg) {
-    const uint64_t k = (nseg + kChunkSegs - 1) / kChunkSegs;
+  explicit Chunks(uint64_t nseg, uint64_t most = kChunkSegs) {
+    const uint64_t k = (nseg + most - 1) / most;
     size = k ? (nseg + k - 1) / k : 1;
   }
 };
@@ -220,6 +242,12 @@ struct Chunks {
 // the next synchronisation (a chunk of Zstd compress scratch is ~12 GB; steady-state calls
 // stay below this and never touch the driver).
 constexpr uint64_t kPoolKeepBytes = 24ull << 30;
+// AUTOPACK compress keeps a whole slot per segment and later candidate (up to three of them):
+// chunks of at most 8192 segments bound that scratch at 3 * 8192 * 65792 B = 1.6 GB (64 KiB
+// segments, element widths 4 and 8), and 8192 one-wave workgroups still cover the chip.
+// Decompress keeps 16 bytes per segment (four index lists): 1 MiB per chunk of 65536 segments.
+constexpr uint64_t kAutoChunkSegs = 8192;
+constexpr uint64_t kAutoDecChunkSegs = 65536;
 
 // index of the error word of `stream`; words run out only after 1000+ distinct foreign
 // streams, after which they share the NULL stream's word (still correct, merely coarser)
@@ -378,9 +406,30 @@ static bool is_runpack(uint32_t codec) {
   return codec >= BITAR_HIP_CODEC_RUNPACK8 && codec <= BITAR_HIP_CODEC_RUNPACK128;
 }
 
+// the five AUTOPACK ids, 40 + log2 of the element width (1, 2, 4, 8 or 16 bytes)
+static bool is_autopack(uint32_t codec) {
+  return codec >= BITAR_HIP_CODEC_AUTOPACK8 && codec <= BITAR_HIP_CODEC_AUTOPACK128;
+}
+
+// AUTOPACK decode: 1 (default) sorts the segments into one index list per format on the device,
+// 0 has every format's decoder look at every segment's tag (DESIGN.md 4.21 has both measured).
+// Read at every call, so that one process can run both forms alternately.
+static bool autopack_lists() {
+  const char* e = std::getenv("BITAR_HIP_AUTOPACK_LISTS");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
+// AUTOPACK compress: 1 (default) runs the later candidates in their store-less form, 0 the
+// codecs' own kernels (DESIGN.md 4.21 has both measured).  Read at every call.
+static bool autopack_storeless() {
+  const char* e = std::getenv("BITAR_HIP_AUTOPACK_STORELESS");
+  return !(e && e[0] == '0' && e[1] == 0);
+}
+
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
   uint64_t bound;
-  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec) || is_runpack(codec))
+  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec) || is_runpack(codec) ||
+      is_autopack(codec))
     bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
@@ -416,7 +465,12 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
     case BITAR_HIP_CODEC_RUNPACK16:
     case BITAR_HIP_CODEC_RUNPACK32:
     case BITAR_HIP_CODEC_RUNPACK64:
-    case BITAR_HIP_CODEC_RUNPACK128: return 0;  // "none": the codec has no matches at all
+    case BITAR_HIP_CODEC_RUNPACK128:
+    case BITAR_HIP_CODEC_AUTOPACK8:
+    case BITAR_HIP_CODEC_AUTOPACK16:
+    case BITAR_HIP_CODEC_AUTOPACK32:
+    case BITAR_HIP_CODEC_AUTOPACK64:
+    case BITAR_HIP_CODEC_AUTOPACK128: return 0;  // "none": the codec has no matches at all
     default: return 0;                          // "unknown": no such codec
   }
 }
@@ -553,7 +607,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
       codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec) && !is_fltpack(codec) &&
-      !is_dictpack(codec) && !is_runpack(codec))
+      !is_dictpack(codec) && !is_runpack(codec) && !is_autopack(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -620,6 +674,79 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
       default: BITAR_RUNPACK(16); break;
     }
 #undef BITAR_RUNPACK
+  }
+  else if (is_autopack(codec)) {
+    // the smallest of the candidates' streams per segment (autopack.hip): RUNPACK straight
+    // into the caller's slots, every later candidate (INTPACK for 1- to 8-byte elements,
+    // DICTPACK for 4 to 16, FLTPACK for 4 and 8) into a stream-ordered scratch slab of its own
+    // with its own sizes (store-less: a segment a later candidate would store gets its size
+    // only, and the select kernel never takes it), then the select kernel.  Chunks of <=
+    // kAutoChunkSegs segments over one allocation.
+    const uint32_t lg = codec - BITAR_HIP_CODEC_AUTOPACK8, w = 1u << lg;
+    const uint32_t extra = (w <= 8 ? 1u : 0u) + (w >= 4 ? 1u : 0u) + (w == 4 || w == 8 ? 1u : 0u);
+    const uint64_t scr_stride = bitar_hip_slot_size(codec, seg);
+    const Chunks ch(nseg, kAutoChunkSegs);
+    const bool lean = autopack_storeless();
+    void* scratch = nullptr;
+    HIP_TRY(hipMallocAsync(&scratch, extra * ch.size * (scr_stride + 4u), s), "scratch allocation");
+    auto* scr = static_cast<uint8_t*>(scratch);
+    auto* ssz = reinterpret_cast<uint32_t*>(scr + extra * ch.size * scr_stride);
+    for (uint64_t c0 = 0; c0 < nseg; c0 += ch.size) {
+      const uint32_t cn = (uint32_t)(nseg - c0 < ch.size ? nseg - c0 : ch.size);
+      const uint64_t cb = c0 * seg, nb = n - cb < (uint64_t)cn * seg ? n - cb : (uint64_t)cn * seg;
+      uint8_t* cslab = slab ? slab + c0 * slot_stride : nullptr;
+      uint8_t* const* cdsts = dsts ? dsts + c0 : nullptr;
+      const uint8_t* cin = in + cb;
+      uint32_t k = 0;  // the next scratch candidate
+#define BITAR_CANDIDATE(kernel, W, to_slab, to_stride, to_dsts, to_sizes)                        \
+  hipLaunchKernelGGL(bitar_hip::kernel<W>, dim3(cn), dim3(64), 0, s, cin, nb, seg, to_slab,      \
+                     to_stride, to_dsts, to_sizes)
+#define BITAR_SCRATCH_CANDIDATE(name, W)                                                         \
+  do {                                                                                           \
+    if (lean)                                                                                    \
+      BITAR_CANDIDATE(name##_compress_candidate_kernel, W, scr + k * ch.size * scr_stride,       \
+                      scr_stride, (uint8_t* const*)nullptr, ssz + k * ch.size);                  \
+    else                                                                                         \
+      BITAR_CANDIDATE(name##_compress_kernel, W, scr + k * ch.size * scr_stride, scr_stride,     \
+                      (uint8_t* const*)nullptr, ssz + k * ch.size);                              \
+    ++k;                                                                                         \
+  } while (0)
+      switch (w) {
+        case 1:
+          BITAR_CANDIDATE(runpack_compress_kernel, 1, cslab, slot_stride, cdsts, d_sizes + c0);
+          BITAR_SCRATCH_CANDIDATE(intpack, 1);
+          break;
+        case 2:
+          BITAR_CANDIDATE(runpack_compress_kernel, 2, cslab, slot_stride, cdsts, d_sizes + c0);
+          BITAR_SCRATCH_CANDIDATE(intpack, 2);
+          break;
+        case 4:
+          BITAR_CANDIDATE(runpack_compress_kernel, 4, cslab, slot_stride, cdsts, d_sizes + c0);
+          BITAR_SCRATCH_CANDIDATE(intpack, 4);
+          BITAR_SCRATCH_CANDIDATE(dictpack, 4);
+          BITAR_SCRATCH_CANDIDATE(fltpack, 4);
+          break;
+        case 8:
+          BITAR_CANDIDATE(runpack_compress_kernel, 8, cslab, slot_stride, cdsts, d_sizes + c0);
+          BITAR_SCRATCH_CANDIDATE(intpack, 8);
+          BITAR_SCRATCH_CANDIDATE(dictpack, 8);
+          BITAR_SCRATCH_CANDIDATE(fltpack, 8);
+          break;
+        default:
+          BITAR_CANDIDATE(runpack_compress_kernel, 16, cslab, slot_stride, cdsts, d_sizes + c0);
+          BITAR_SCRATCH_CANDIDATE(dictpack, 16);
+          break;
+      }
+#undef BITAR_SCRATCH_CANDIDATE
+#undef BITAR_CANDIDATE
+      hipLaunchKernelGGL(bitar_hip::autopack_select_kernel, dim3((cn + 3) / 4), dim3(256), 0, s,
+                         static_cast<const uint8_t*>(scr), scr_stride,
+                         static_cast<const uint32_t*>(ssz), (uint32_t)ch.size, extra + 1u, cn,
+                         cslab, slot_stride, cdsts, d_sizes + c0);
+    }
+    const hipError_t le = hipGetLastError();
+    HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+    HIP_TRY(le, "compress launch");
   }
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
     SegOrder ord;
@@ -981,7 +1108,8 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   if (is_fltpack(codec)) codec = BITAR_HIP_CODEC_FLTPACK32;  // (likewise)
   if (is_dictpack(codec)) codec = BITAR_HIP_CODEC_DICTPACK32;  // (likewise)
   if (is_runpack(codec)) codec = BITAR_HIP_CODEC_RUNPACK8;  // (likewise)
-  if (codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
+  if (is_autopack(codec)) codec = BITAR_HIP_CODEC_AUTOPACK8;  // (the format too)
+  if (codec != BITAR_HIP_CODEC_AUTOPACK8 && codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
       codec != BITAR_HIP_CODEC_DICTPACK32 && codec != BITAR_HIP_CODEC_RUNPACK8 &&
       codec != BITAR_HIP_CODEC_LZ4 &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
@@ -1019,6 +1147,45 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   else if (codec == BITAR_HIP_CODEC_RUNPACK8) {
     hipLaunchKernelGGL(bitar_hip::runpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
                        slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
+  }
+  else if (codec == BITAR_HIP_CODEC_AUTOPACK8) {
+    // each segment to the decoder its tag names (autopack.hip): the route kernel rejects the
+    // segments no format claims and sorts the others into one index list per format, with the
+    // counts, in a stream-ordered scratch; each format's listed decoder then runs over nseg
+    // workgroups of which the first count[f] take a segment.  No host round trip.
+    const bool lists = autopack_lists();
+    const Chunks ch(nseg, kAutoDecChunkSegs);
+    void* scratch = nullptr;
+    if (lists) HIP_TRY(hipMallocAsync(&scratch, 16u * ch.size + 16u, s), "scratch allocation");
+    auto* counts = static_cast<uint32_t*>(scratch);
+    uint32_t* ew = err_word(ctx, s);
+    hipError_t me = hipSuccess;
+    for (uint64_t c0 = 0; c0 < nseg && me == hipSuccess; c0 += ch.size) {
+      const uint32_t cn = (uint32_t)(nseg - c0 < ch.size ? nseg - c0 : ch.size);
+      const uint8_t* const* csrcs = srcs ? srcs + c0 : nullptr;
+      const uint8_t* cslab = slab ? slab + c0 * stride : nullptr;
+      const uint32_t* csz = d_sizes + c0;
+      uint8_t* cout = out + c0 * seg;
+      uint32_t* cprod = d_produced + c0;
+      uint32_t* cl = lists ? counts + 4 : nullptr;
+      if (lists) me = hipMemsetAsync(counts, 0, 16, s);
+      if (me != hipSuccess) break;
+      hipLaunchKernelGGL(bitar_hip::autopack_route_kernel, dim3((cn + 255) / 256), dim3(256), 0, s,
+                         csrcs, cslab, stride, csz, cn, cprod, ew, cl, counts);
+#define BITAR_LISTED(kernel, f)                                                                 \
+  hipLaunchKernelGGL(bitar_hip::kernel, dim3(cn), dim3(64), 0, s, csrcs, cslab, stride, csz, cn, \
+                     seg, cout, cprod, ew, lists ? cl + (uint64_t)(f)*cn : nullptr,             \
+                     lists ? counts + (f) : nullptr)
+      BITAR_LISTED(intpack_decompress_listed_kernel, 0);
+      BITAR_LISTED(fltpack_decompress_listed_kernel, 1);
+      BITAR_LISTED(dictpack_decompress_listed_kernel, 2);
+      BITAR_LISTED(runpack_decompress_listed_kernel, 3);
+#undef BITAR_LISTED
+    }
+    const hipError_t le = hipGetLastError();
+    if (scratch) HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+    HIP_TRY(me, "clear counts");
+    HIP_TRY(le, "decompress launch");
   }
   else if (codec == BITAR_HIP_CODEC_LZ4)
   {

@@ -170,7 +170,29 @@ enum bitar_hip_codec {
   BITAR_HIP_CODEC_RUNPACK16 = 33,
   BITAR_HIP_CODEC_RUNPACK32 = 34,
   BITAR_HIP_CODEC_RUNPACK64 = 35,
-  BITAR_HIP_CODEC_RUNPACK128 = 36
+  BITAR_HIP_CODEC_RUNPACK128 = 36,
+  /* AUTOPACK: per segment the smallest of the applicable codecs above, for
+   * columns whose shape the caller does not know or that changes from segment to segment.  The
+   * id is 40 + log2(w) for w = 1, 2, 4, 8 or 16 bytes.  AUTOPACK has no format of its own.  For
+   * a segment of L bytes the candidates are, in this order,
+   *   w = 1, 2    RUNPACK, INTPACK
+   *   w = 4, 8    RUNPACK, INTPACK, DICTPACK, FLTPACK
+   *   w = 16      RUNPACK, DICTPACK
+   * and the segment's stream is the shortest of the candidates' streams for that segment and
+   * width, exactly as their own ids write them; a tie goes to the earlier candidate.  Nothing is
+   * added: no wrapper byte, no new tag.  So every AUTOPACK stream decodes under its codec's own
+   * id as well, a segment no candidate packs is RUNPACK's stored form (tag 0x78 | log2(w): all
+   * candidates tie at 4 + L), and the size is never above any single candidate's.  The decoder
+   * looks at the high nibble of byte 0: 4, 5, 6 or 7 gives the segment to INTPACK's, FLTPACK's,
+   * DICTPACK's or RUNPACK's decoder, with that decoder's every rule and verdict (and what a
+   * rejected segment of that format may have written); any other nibble, and a stream of size 0,
+   * is rejected with its output range untouched.  Every AUTOPACK id decodes every width and all
+   * four formats. */
+  BITAR_HIP_CODEC_AUTOPACK8 = 40,
+  BITAR_HIP_CODEC_AUTOPACK16 = 41,
+  BITAR_HIP_CODEC_AUTOPACK32 = 42,
+  BITAR_HIP_CODEC_AUTOPACK64 = 43,
+  BITAR_HIP_CODEC_AUTOPACK128 = 44
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -192,6 +214,12 @@ enum bitar_hip_codec {
   ((width) == 1 ? BITAR_HIP_CODEC_RUNPACK8 : (width) == 2 ? BITAR_HIP_CODEC_RUNPACK16 : \
    (width) == 4 ? BITAR_HIP_CODEC_RUNPACK32 : (width) == 8 ? BITAR_HIP_CODEC_RUNPACK64 : \
    BITAR_HIP_CODEC_RUNPACK128)
+
+/* The AUTOPACK id of an element width of 1, 2, 4, 8 or 16 bytes. */
+#define BITAR_HIP_CODEC_AUTOPACK(width) \
+  ((width) == 1 ? BITAR_HIP_CODEC_AUTOPACK8 : (width) == 2 ? BITAR_HIP_CODEC_AUTOPACK16 : \
+   (width) == 4 ? BITAR_HIP_CODEC_AUTOPACK32 : (width) == 8 ? BITAR_HIP_CODEC_AUTOPACK64 : \
+   BITAR_HIP_CODEC_AUTOPACK128)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -244,14 +272,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK and RUNPACK, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK and AUTOPACK, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK and RUNPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK and AUTOPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
