@@ -322,7 +322,19 @@ int bitar_hip_compress_scattered(bitar_hip_ctx* ctx, void* stream, uint32_t code
  * (reference device.cc:248-254).  seg <= 65536, except for Zstd: <= 2^30, so that a whole
  * stock frame of any content size can be one segment.  Asynchronous on `stream`.
  * Replaces one CompressDevice::Decompress call (reference src/device.cc:240-318,
- * src/memory.cc:432-505). */
+ * src/memory.cc:432-505).
+ *
+ * What a call writes (any alignment of d_out and of the sources; pinned with guard bytes
+ * around every buffer by tests/test_gpu_canaries.py):
+ *   - segment i writes only inside [d_out + i*seg, d_out + (i+1)*seg);
+ *   - of that range the first d_produced[i] bytes are the segment's output, the bytes past
+ *     them are unspecified (the lane decoders copy in 8-byte words that run up to 32 bytes
+ *     ahead of the output position, and the Zstd lane kernels stage literals at the range's
+ *     tail), so a segment that produces 0 bytes leaves its range as it was;
+ *   - a rejected segment (BITAR_HIP_SEGMENT_ERROR) may have written anywhere inside its own
+ *     range, and nowhere else;
+ *   - d_produced[0, nseg) is written; nothing else is: not the sources, not d_sizes, no byte
+ *     before d_out or from d_out + nseg*seg on, whatever `capacity` is. */
 int bitar_hip_decompress(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
                          const void* const* d_srcs, const uint32_t* d_sizes, uint32_t nseg,
                          uint32_t seg, void* d_out, uint64_t capacity, uint32_t* d_produced);

@@ -252,3 +252,165 @@ def lz4_end_rule_cases():
                 seqs.append((lits, 5, ml))
                 cases.append(lz4_block(seqs, bytes(rng.integers(0, 256, fl).astype(np.uint8))))
     return cases
+
+
+# ---- the canary tests' streams (tests/test_canary_model.py, tests/test_gpu_canaries.py) ----
+def spacer(codec):
+    """the codec's empty stream: decodes to 0 bytes, so its output range stays untouched"""
+    if codec in (O.CODEC_LZ4, O.CODEC_LZ4_WIDE):
+        return b"\x00"  # one token: no literals, no match
+    if codec in (O.CODEC_DEFLATE, O.CODEC_DEFLATE_DYN):
+        return b"\x03\x00"  # a final fixed-Huffman block holding the end-of-block code alone
+    if codec == O.CODEC_ZSTD:
+        return bytes.fromhex("28b52ffd2000010000")  # single segment, size 0, one empty raw block
+    raise ValueError(codec)
+
+
+# match offsets by the branch of lanes::copy_match (bitar_amd/csrc/lane_copy.hip.h) they take
+OFFSET_CLASSES = ((1, 7), (8, 15), (16, 31), (32, 255))
+TAIL_SEQUENCES = 16
+# (literals, offset class, match length) behind the short sequences of a "long" tail: matches
+# above 16 bytes take copy_match's loops, whose last store reaches furthest past the match --
+# 31 bytes where the offset is >= 32 and the length is 1 mod 32, as in the last one
+LONG_SEQUENCES = ((3, 2, 17), (1, 3, 33), (2, 1, 41), (1, 0, 19), (5, 3, 65), (1, 2, 49),
+                  (2, 3, 97), (1, 3, 33))
+
+
+def tail_shapes(rng, min_match, have, far=0, long=False):
+    """(literals, offset, match length) of the TAIL_SEQUENCES short sequences that end an
+    end-room plain: every literal run length 1..16 once, match lengths min_match..16, the
+    offset classes in turn, over a body of `have` bytes; with far, the last class reaches up to
+    `far` bytes back; with long, LONG_SEQUENCES follow"""
+    shapes = []
+    for k in range(TAIL_SEQUENCES):
+        lo, hi = OFFSET_CLASSES[k % 4]
+        hi = min(hi, have)
+        if far and k % 4 == 3 and k % 8 == 7:
+            lo, hi = far // 2, far
+        shapes.append((1 + (5 * k) % 16, int(rng.integers(lo, hi + 1)),
+                       min_match + (3 * k) % (17 - min_match)))
+    for nlit, cls, ml in LONG_SEQUENCES if long else ():
+        lo, hi = OFFSET_CLASSES[cls]
+        shapes.append((nlit, int(rng.integers(lo, min(hi, have) + 1)), ml))
+    return shapes
+
+
+def apply_tail(body, shapes, rng):
+    """body + the tail the shapes describe -> (plain, [(literal bytes, offset, length)])"""
+    plain = bytearray(body)
+    seqs = []
+    for nlit, off, ml in shapes:
+        lits = bytes(rng.integers(0, 256, nlit).astype(np.uint8))
+        plain += lits
+        assert off <= len(plain)
+        for _ in range(ml):  # byte by byte: offsets below the length overlap themselves
+            plain.append(plain[-off])
+        seqs.append((lits, off, ml))
+    return bytes(plain), seqs
+
+
+def zstd_without_content_size(frame):
+    """the same blocks behind a frame header that carries no Frame_Content_Size (RFC 8878
+    3.1.1.1: no single-segment flag, a 64 KiB window descriptor)"""
+    assert frame[:4] == bytes.fromhex("28b52ffd")
+    fhd = frame[4]
+    single, did = (fhd >> 5) & 1, fhd & 3
+    assert not fhd & 4, "content checksum"
+    hdr = 1 + (0 if single else 1) + (0, 1, 2, 4)[did] + ((1 if single else 0), 2, 4, 8)[fhd >> 6]
+    return frame[:4] + b"\x00\x30" + frame[4 + hdr:]
+
+
+def zstd_literal_types(frame):
+    """Literals_Block_Type of every compressed block of a frame (0 raw, 1 RLE, 2 Huffman,
+    3 treeless)"""
+    fhd = frame[4]
+    single, did = (fhd >> 5) & 1, fhd & 3
+    at = 5 + (0 if single else 1) + (0, 1, 2, 4)[did] + ((1 if single else 0), 2, 4, 8)[fhd >> 6]
+    types = []
+    while True:
+        h = int.from_bytes(frame[at:at + 3], "little")
+        last, btype, size = h & 1, (h >> 1) & 3, h >> 3
+        at += 3
+        if btype == 2:
+            types.append(frame[at] & 3)
+        at += 1 if btype == 1 else size
+        if last:
+            return types
+
+
+def _end_room(name, stream, plain, shapes, final):
+    return {"name": name, "stream": stream, "plain": plain, "shapes": shapes, "final": final}
+
+
+def end_room_streams(codec):
+    """streams whose plain ends in TAIL_SEQUENCES short sequences (tail_shapes) and, for LZ4,
+    the final literals the block format requires: dicts of name, stream, plain, shapes (the
+    tail's construction) and final (bytes of plain behind the last match)"""
+    out = []
+    if codec == O.CODEC_LZ4:
+        rng = np.random.default_rng(3201)
+        for body_n, final_n, far in ((64, 5, 0), (300, 6, 0), (1001, 9, 0), (5003, 12, 0),
+                                     (20011, 16, 15000), (2002, 5, 0)):
+            body = bytes(rng.integers(0, 256, body_n).astype(np.uint8))
+            shapes = tail_shapes(rng, 4, body_n, far, long=body_n == 2002)
+            plain, seqs = apply_tail(body, shapes, rng)
+            # (the block format: the last match starts >= 12 bytes before the end)
+            final_n = max(final_n, 12 - seqs[-1][2])
+            final = bytes(rng.integers(0, 256, final_n).astype(np.uint8))
+            block = lz4_block([(body + seqs[0][0],) + seqs[0][1:]] + seqs[1:], final)
+            out.append(_end_room(f"lz4-{'long-' if body_n == 2002 else ''}{body_n}", block,
+                                 plain + final, shapes, final_n))
+        # one whose third token is a short match 11000 bytes back with most of the block still
+        # ahead: the near kernel defers such a segment when it sees the token
+        # (lz4_decompress.hip, FARK = false), so the far-history kernel decodes its end
+        head = bytes(rng.integers(0, 256, 12000).astype(np.uint8))
+        lits = bytes(rng.integers(0, 256, 3).astype(np.uint8))
+        body = head + head[-100:-92] + lits
+        body += body[-11000:-11000 + 8] + bytes(rng.integers(0, 256, 8000).astype(np.uint8))
+        shapes = tail_shapes(rng, 4, len(body), 15000)
+        plain, seqs = apply_tail(body, shapes, rng)
+        final = bytes(rng.integers(0, 256, 13).astype(np.uint8))
+        block = lz4_block([(head, 100, 8), (lits, 11000, 8),
+                           (body[-8000:] + seqs[0][0],) + seqs[0][1:]] + seqs[1:], final)
+        out.append(_end_room("lz4-deferred", block, plain + final, shapes, 13))
+        return out
+    if codec in (O.CODEC_DEFLATE, O.CODEC_DEFLATE_DYN):
+        rng = np.random.default_rng(3202)
+        for kind, body_n, far in ((6, 3003, 0), (1, 20001, 15000), (2, 6010, 0), (6, 2002, 0)):
+            body = O.fill(kind, 61 + kind, body_n).tobytes()
+            shapes = tail_shapes(rng, 3, body_n, far, long=body_n == 2002)
+            plain, _ = apply_tail(body, shapes, rng)
+            r, fixed = O.deflate_fixed(plain)
+            assert r == 0
+            r, dyn = O.deflate_dynamic(plain)
+            assert r == 0
+            z = zlib.compressobj(1, zlib.DEFLATED, -15, 8, zlib.Z_FIXED)
+            zfixed = z.compress(plain) + z.flush()
+            z = zlib.compressobj(1, zlib.DEFLATED, -15, 8, zlib.Z_DEFAULT_STRATEGY)
+            zdyn = z.compress(plain) + z.flush()
+            for tag, s in (("fixed", fixed), ("dynamic", dyn), ("zlib-fixed", zfixed),
+                           ("zlib-1", zdyn)):
+                out.append(_end_room(f"deflate-{tag}-{'long-' if body_n == 2002 else ''}{body_n}",
+                                     s, plain, shapes, 0))
+        return out
+    if codec == O.CODEC_ZSTD:
+        rng = np.random.default_rng(3203)
+        Z = libzstd()
+        for kind, body_n, far in ((6, 4003, 0), (0, 1501, 0), (2, 20006, 15000), (0, 2002, 0)):
+            body = O.fill(kind, 71 + kind, body_n).tobytes()
+            shapes = tail_shapes(rng, 3, body_n, far, long=body_n == 2002)
+            plain, _ = apply_tail(body, shapes, rng)
+            r, ours = O.zstd_compress(plain)
+            assert r == 0
+            body_n = f"{'long-' if body_n == 2002 else ''}{body_n}"
+            out.append(_end_room(f"zstd-ours-{body_n}", ours, plain, shapes, 0))
+            out.append(_end_room(f"zstd-ours-nofcs-{body_n}", zstd_without_content_size(ours),
+                                 plain, shapes, 0))
+            if Z is not None:
+                n = len(plain)
+                buf = ctypes.create_string_buffer(n + 1024)
+                r = Z.ZSTD_compress(buf, n + 1024, plain, n, 1)
+                assert not Z.ZSTD_isError(r)
+                out.append(_end_room(f"zstd-lib1-{body_n}", buf.raw[:r], plain, shapes, 0))
+        return out
+    raise ValueError(codec)
