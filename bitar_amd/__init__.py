@@ -17,6 +17,7 @@ CODEC_DEFLATE = 2
 CODEC_ZSTD = 3
 CODEC_DEFLATE_DYNAMIC = 4  # HuffmanEncoding::DYNAMIC (decoded as CODEC_DEFLATE)
 CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio operating point
+CODEC_SNAPPY = 6  # one raw Snappy stream per segment (the LZ4 parse; decodes stock raw Snappy)
 # INTPACK: frame-of-reference bit packing of 1 / 2 / 4 / 8-byte integers (any of them decodes)
 CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
 # FLTPACK: decimal-scaled bit packing of 4-byte floats / 8-byte doubles (either id decodes both)

@@ -59,9 +59,12 @@ using Class_HIP_GFX950 =
 /// streams RUNPACK, INTPACK, DICTPACK and FLTPACK give at element_width() (1, 2, 4, 8 or 16; a
 /// codec is tried at the widths it has), and decodes each segment by its tag -- for columns whose
 /// shape is not known in advance or changes along the column.
+/// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
+/// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
+/// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
-  AUTOPACK = 8
+  AUTOPACK = 8, SNAPPY = 9
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };

@@ -15,6 +15,7 @@ std::string_view ToString(Codec c) {
     case Codec::DICTPACK: return "DICTPACK";
     case Codec::RUNPACK: return "RUNPACK";
     case Codec::AUTOPACK: return "AUTOPACK";
+    case Codec::SNAPPY: return "SNAPPY";
   }
   return "UNKNOWN";
 }

@@ -304,6 +304,7 @@ std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
     case Codec::AUTOPACK: return BITAR_HIP_CODEC_AUTOPACK(element_width);
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
+    case Codec::SNAPPY: return BITAR_HIP_CODEC_SNAPPY;
     default:
       return c.huffman_enc() == HuffmanEncoding::FIXED ? BITAR_HIP_CODEC_DEFLATE
                                                       : BITAR_HIP_CODEC_DEFLATE_DYNAMIC;
@@ -770,7 +771,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
       configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::INTPACK &&
       configuration_->codec() != Codec::FLTPACK && configuration_->codec() != Codec::DICTPACK &&
-      configuration_->codec() != Codec::RUNPACK && configuration_->codec() != Codec::AUTOPACK)
+      configuration_->codec() != Codec::RUNPACK && configuration_->codec() != Codec::AUTOPACK &&
+      configuration_->codec() != Codec::SNAPPY)
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
   if (configuration_->max_sgl_segs() < 1) configuration_->set_max_sgl_segs(1);
@@ -837,7 +839,7 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   // the reach of the encoder this configuration runs (bitar_hip_max_distance: 2560 B -> 2^12,
   // the wide LZ4 parse 14848 B -> 2^14); a requested window is validated and kept as the
   // reference keeps it.  Any window from the reach up to the format's maximum (DEFLATE 2^15,
-  // LZ4 / single-segment Zstd 2^16) is honoured -- every stream the encoder writes is valid for
+  // LZ4 / Snappy / single-segment Zstd 2^16) is honoured -- every stream the encoder writes is valid for
   // it, and the decoders take the format's full window -- a smaller one is refused.
   // encoder_window() reports the reach whatever was requested.
   const std::uint32_t reach =

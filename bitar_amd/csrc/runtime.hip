@@ -27,6 +27,11 @@ template <bool FARK>
 __global__ void lz4_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                       const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                       uint32_t*, unsigned long long*, const uint32_t*);
+__global__ void snappy_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
+                                       uint8_t* const*, uint32_t*, const uint32_t*);
+__global__ void snappy_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
+                                         const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
+                                         uint32_t*, const uint32_t*);
 __global__ void seg_cost_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
 __global__ void order_hist_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
                                   uint32_t*);
@@ -433,6 +438,8 @@ uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
     bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
+  else if (codec == BITAR_HIP_CODEC_SNAPPY)
+    bound = (uint64_t)seg + 6u;                         // the stored form: varint + tag + segment
   else if (codec == BITAR_HIP_CODEC_DEFLATE || codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC)
     bound = ((uint64_t)seg * 9 + 7) / 8 + 16u;          // fixed Huffman, 9 bits/literal
   else if (codec == BITAR_HIP_CODEC_ZSTD)  // oracle bo_zstd_bound: one block, raw if larger
@@ -448,6 +455,7 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
   // DEFLATE and Zstd, a 16 KiB ring for the wide LZ4 parse (compress.hip, lz4_wide)
   switch (codec) {
     case BITAR_HIP_CODEC_LZ4:
+    case BITAR_HIP_CODEC_SNAPPY:  // (the LZ4 codec's parse)
     case BITAR_HIP_CODEC_DEFLATE:
     case BITAR_HIP_CODEC_DEFLATE_DYNAMIC:
     case BITAR_HIP_CODEC_ZSTD: return 4096u - 1536u;
@@ -606,7 +614,8 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (int r = enter(ctx)) return r;
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
-      codec != BITAR_HIP_CODEC_LZ4_WIDE && !is_intpack(codec) && !is_fltpack(codec) &&
+      codec != BITAR_HIP_CODEC_LZ4_WIDE && codec != BITAR_HIP_CODEC_SNAPPY &&
+      !is_intpack(codec) && !is_fltpack(codec) &&
       !is_dictpack(codec) && !is_runpack(codec) && !is_autopack(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
@@ -759,6 +768,15 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
       hipLaunchKernelGGL((bitar_hip::lz4_compress_kernel<16384, 12>), dim3((uint32_t)nseg),
                          dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts, d_sizes,
                          err_word(ctx, s), ord.order);
+    if (int r = ord.release()) return r;
+  }
+  else if (codec == BITAR_HIP_CODEC_SNAPPY) {
+    // the LZ4 parse with the Snappy emitter (snappy.hip), dispatched as LZ4 is; a segment
+    // never fails (the stored form fits every slot), so the kernel takes no error word
+    SegOrder ord;
+    if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
+    hipLaunchKernelGGL(bitar_hip::snappy_compress_kernel, dim3((uint32_t)nseg), dim3(64), 0, s,
+                       in, n, seg, slab, slot_stride, dsts, d_sizes, ord.order);
     if (int r = ord.release()) return r;
   }
   else if (codec == BITAR_HIP_CODEC_DEFLATE) {
@@ -1111,7 +1129,7 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   if (is_autopack(codec)) codec = BITAR_HIP_CODEC_AUTOPACK8;  // (the format too)
   if (codec != BITAR_HIP_CODEC_AUTOPACK8 && codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
       codec != BITAR_HIP_CODEC_DICTPACK32 && codec != BITAR_HIP_CODEC_RUNPACK8 &&
-      codec != BITAR_HIP_CODEC_LZ4 &&
+      codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_SNAPPY &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (nseg == 0) return 0;  // reference device.cc:244-246
@@ -1200,6 +1218,16 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
     hipLaunchKernelGGL(bitar_hip::lz4_decompress_kernel<true>, dim3(nseg), dim3(64), 0, s, srcs,
                        slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
                        stats, ord.order);
+    if (int r = ord.release()) return r;
+  }
+  else if (codec == BITAR_HIP_CODEC_SNAPPY) {
+    // one kernel (snappy.hip): far history is read back from HBM inside it.  Cost key: the
+    // coded size, largest first; stored segments (one literal: copies) last
+    SegOrder ord;
+    if (int r = ord.make(ctx, s, nseg, d_sizes, [](uint32_t*) {}, seg)) return r;
+    hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
+                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
+                       ord.order);
     if (int r = ord.release()) return r;
   }
   else if (codec == BITAR_HIP_CODEC_DEFLATE) {

@@ -52,6 +52,30 @@ enum bitar_hip_codec {
                                           at a lower speed; the streams are ordinary LZ4 blocks
                                           (decoded like LZ4).  The C++ front-end selects it for
                                           Codec::LZ4 at level() >= 2 (bitar/config.h). */
+  /* SNAPPY: one RAW Snappy stream per segment (no framing format), readable
+   * by every stock Snappy decoder; the decoder reads any stock raw stream of <= 65536 bytes.
+   * A segment of n bytes:
+   *   preamble    n as a minimal varint (<= 3 bytes; n = 0: the single byte 00)
+   *   elements    the sequences of BITAR_HIP_CODEC_LZ4's parse (distance <= 2560), each as
+   *               - one literal element for a non-empty literal run: tag (len-1) << 2 for
+   *                 len-1 < 60, tag 60 << 2 + 1 length byte for len-1 < 256, else tag 61 << 2 +
+   *                 2 length bytes (little-endian), then the bytes;
+   *               - the match split by stock Snappy's rule (while len >= 68 a piece of 64, a
+   *                 piece of 60 if len > 64, then the rest, 4..64), each piece a copy-1 element
+   *                 (2 bytes: tag 1 | (len-4) << 2 | (offset >> 8) << 5, offset low byte) if
+   *                 4 <= len <= 11 and offset < 2048, else a copy-2 element (3 bytes: tag
+   *                 2 | (len-1) << 2, LE16 offset); copy-4 is never written;
+   *               the trailing literals are a last literal element.
+   *   stored      a stream that is not smaller than preamble + ONE literal element holding the
+   *               whole segment (or that overran its slot) is written in that form, so a stream
+   *               is <= n + 6 bytes and compress never fails for lack of space.
+   * The decoder follows stock Snappy: the varint may be non-minimal (<= 5 bytes, the fifth
+   * below 16); literal length codes 60..63 and copy-4 are legal; a copy with offset 0 or beyond
+   * the bytes produced so far rejects (offset == produced is fine, overlapping copies
+   * replicate); an element reading past the input rejects; the elements must consume the input
+   * exactly and produce exactly the declared length.  A declared length above seg fails the
+   * segment.  No byte outside the segment's seg output bytes is written in any case. */
+  BITAR_HIP_CODEC_SNAPPY = 6,
   /* INTPACK: frame-of-reference bit packing of little-endian integer
    * elements, for columns of narrow range (dictionary indices, small integers, sorted keys,
    * timestamps, string offsets).  The id is 8 + log2(element width in bytes); no reference
