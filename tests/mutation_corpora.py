@@ -169,6 +169,34 @@ def inflate_fixed_cases():
     return cases
 
 
+def inflate_handbuilt_cases():
+    """the hand-built RFC 1951 corpus (tests/deflate_streams.py), every stream as written"""
+    import deflate_streams as DS
+    return [c[2] for c in DS.corpus()]
+
+
+def handbuilt_sources():
+    """(stream, hot): six hand-built streams -- the 15-bit literal and distance ladders, the
+    single distance code, the repeat item across HLIT, fixed -> dynamic -> fixed, far history
+    behind a long stored block -- and the byte range of each one's dynamic block header"""
+    import deflate_streams as DS
+    by_name = {c[0]: c[2] for c in DS.corpus()}
+    srcs = []
+    for name in DS.MUTATION_BASES:
+        s = by_name[name]
+        b = next(b for b in DS.walk(s)["blocks"] if b["type"] == 2)
+        srcs.append((s, (b["hdr_bit"] >> 3, (b["body_bit"] >> 3) + 1)))
+    return srcs
+
+
+def inflate_handbuilt_mutation_cases():
+    rng = np.random.default_rng(1953)
+    cases = []
+    for stream, hot in handbuilt_sources():
+        cases += mutations(stream, rng, 40, hot=hot)
+    return cases
+
+
 def zstd_cases():
     rng = np.random.default_rng(8878)
     srcs = zstd_sources()

@@ -387,6 +387,8 @@ CORPORA = {
     "inflate-dynamic": (M.inflate_dynamic_cases, O.CODEC_DEFLATE_DYN, 65536, 480),
     "inflate-dynamic-fixed-hint": (M.inflate_dynamic_cases, O.CODEC_DEFLATE, 65536, 480),
     "inflate-fixed": (M.inflate_fixed_cases, O.CODEC_DEFLATE, 65536, 192),
+    "inflate-handbuilt": (M.inflate_handbuilt_cases, O.CODEC_DEFLATE_DYN, 65536, 250),
+    "inflate-handbuilt-fixed-hint": (M.inflate_handbuilt_cases, O.CODEC_DEFLATE, 65536, 250),
     "zstd": (M.zstd_cases, O.CODEC_ZSTD, 65536, 539),
     "lz4-far": (M.lz4_far_cases, O.CODEC_LZ4, 65536, 240),
     "lz4-near": (M.lz4_near_cases, O.CODEC_LZ4, 65536, 240),

@@ -88,6 +88,16 @@ def test_inflate_fixed_and_stored_mutations_like_oracle(eng, counting_inflate):
     _check_like_oracle(eng, O.CODEC_DEFLATE, M.inflate_fixed_cases(), O.inflate)
 
 
+@pytest.mark.parametrize("codec", [O.CODEC_DEFLATE_DYN, O.CODEC_DEFLATE], ids=["dyn", "fixed-hint"])
+def test_inflate_handbuilt_mutations_like_oracle(eng, counting_inflate, codec):
+    """Six hand-built streams (tests/deflate_streams.py: 15-bit literal and distance codes, a
+    single distance code, a repeat item across HLIT, fixed -> dynamic -> fixed, far history
+    behind a long stored block), mutated in their dynamic block headers."""
+    cases = M.inflate_handbuilt_mutation_cases()
+    n_ok = _check_like_oracle(eng, codec, cases, O.inflate)
+    assert 0 < n_ok < len(cases)
+
+
 # ---- Zstd: hand-off -> phase A (seqdec) -> phase B (exec) ---------------------------------
 @pytest.fixture(params=[16, 0], ids=["lanes16-seq", "wave-seq"])
 def counting_zstd(request, eng):

@@ -108,10 +108,12 @@ def _corpus(srcs, rng, count, hot):
     return cases
 
 
-@pytest.mark.parametrize("which", ["gpu_corpora", "extended"])
+@pytest.mark.parametrize("which", ["gpu_corpora", "extended", "handbuilt"])
 def test_inflate_verdicts_match_zlib(which):
     if which == "gpu_corpora":
         cases = M.inflate_dynamic_cases() + M.inflate_fixed_cases()
+    elif which == "handbuilt":  # (tests/deflate_streams.py: the corpus and mutations of six of it)
+        cases = M.inflate_handbuilt_cases() + M.inflate_handbuilt_mutation_cases()
     else:
         rng = np.random.default_rng(4000)
         srcs = M.dynamic_sources() + M.fixed_sources()
