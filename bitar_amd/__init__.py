@@ -18,18 +18,26 @@ CODEC_ZSTD = 3
 CODEC_DEFLATE_DYNAMIC = 4  # HuffmanEncoding::DYNAMIC (decoded as CODEC_DEFLATE)
 CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio operating point
 CODEC_SNAPPY = 6  # one raw Snappy stream per segment (the LZ4 parse; decodes stock raw Snappy)
-# INTPACK: frame-of-reference bit packing of 1 / 2 / 4 / 8-byte integers (any of them decodes)
-CODEC_INTPACK8, CODEC_INTPACK16, CODEC_INTPACK32, CODEC_INTPACK64 = 8, 9, 10, 11
-# FLTPACK: decimal-scaled bit packing of 4-byte floats / 8-byte doubles (either id decodes both)
-CODEC_FLTPACK32, CODEC_FLTPACK64 = 18, 19
-# DICTPACK: per-segment dictionary + bit-packed indices of 4 / 8 / 16-byte elements (any id decodes)
-CODEC_DICTPACK32, CODEC_DICTPACK64, CODEC_DICTPACK128 = 26, 27, 28
-# RUNPACK: per-segment run lengths of 1 / 2 / 4 / 8 / 16-byte elements (any id decodes)
-CODEC_RUNPACK8, CODEC_RUNPACK16, CODEC_RUNPACK32, CODEC_RUNPACK64, CODEC_RUNPACK128 = \
-    32, 33, 34, 35, 36
-# AUTOPACK: per segment the smallest of the applicable four above (any id decodes all of them)
-CODEC_AUTOPACK8, CODEC_AUTOPACK16, CODEC_AUTOPACK32, CODEC_AUTOPACK64, CODEC_AUTOPACK128 = \
-    40, 41, 42, 43, 44
+# The column codecs: name -> (base id, high nibble of a stream's byte 0, element widths in bytes).
+# The id of a width is base + log2(width): CODEC_<NAME><8 * width>, e.g. CODEC_INTPACK32 = 10,
+# and any id of a family decodes all its widths.
+#   INTPACK   frame-of-reference bit packing of integers
+#   FLTPACK   decimal-scaled bit packing of floats / doubles
+#   DICTPACK  per-segment dictionary + bit-packed indices
+#   RUNPACK   per-segment run lengths
+#   AUTOPACK  per segment the smallest of the applicable four above (no format of its own: any id
+#             decodes all of them)
+COLUMN_CODECS = {
+    "INTPACK": (8, 4, (1, 2, 4, 8)),
+    "FLTPACK": (16, 5, (4, 8)),
+    "DICTPACK": (24, 6, (4, 8, 16)),
+    "RUNPACK": (32, 7, (1, 2, 4, 8, 16)),
+    "AUTOPACK": (40, None, (1, 2, 4, 8, 16)),
+}
+_COLUMN_IDS = {name: {w: base + w.bit_length() - 1 for w in widths}
+               for name, (base, _, widths) in COLUMN_CODECS.items()}
+globals().update({f"CODEC_{name}{8 * w}": i for name, ids in _COLUMN_IDS.items()
+                  for w, i in ids.items()})
 SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
@@ -155,47 +163,38 @@ def slot_size(codec, seg):
     return int(lib().bitar_hip_slot_size(codec, seg))
 
 
+def _column_codec(name, width):
+    try:
+        return _COLUMN_IDS[name][width]
+    except (KeyError, TypeError):
+        *most, last = map(str, COLUMN_CODECS[name][2])
+        raise ValueError(f"{name} element width must be {', '.join(most)} or {last}, "
+                         f"not {width!r}") from None
+
+
 def codec_intpack(width):
     """the INTPACK codec id of an element width of 1, 2, 4 or 8 bytes"""
-    try:
-        return {1: CODEC_INTPACK8, 2: CODEC_INTPACK16, 4: CODEC_INTPACK32,
-                8: CODEC_INTPACK64}[width]
-    except (KeyError, TypeError):
-        raise ValueError(f"INTPACK element width must be 1, 2, 4 or 8, not {width!r}") from None
+    return _column_codec("INTPACK", width)
 
 
 def codec_fltpack(width):
     """the FLTPACK codec id of an element width of 4 (float32) or 8 (float64) bytes"""
-    try:
-        return {4: CODEC_FLTPACK32, 8: CODEC_FLTPACK64}[width]
-    except (KeyError, TypeError):
-        raise ValueError(f"FLTPACK element width must be 4 or 8, not {width!r}") from None
+    return _column_codec("FLTPACK", width)
 
 
 def codec_dictpack(width):
     """the DICTPACK codec id of an element width of 4, 8 or 16 bytes"""
-    try:
-        return {4: CODEC_DICTPACK32, 8: CODEC_DICTPACK64, 16: CODEC_DICTPACK128}[width]
-    except (KeyError, TypeError):
-        raise ValueError(f"DICTPACK element width must be 4, 8 or 16, not {width!r}") from None
+    return _column_codec("DICTPACK", width)
 
 
 def codec_runpack(width):
     """the RUNPACK codec id of an element width of 1, 2, 4, 8 or 16 bytes"""
-    try:
-        return {1: CODEC_RUNPACK8, 2: CODEC_RUNPACK16, 4: CODEC_RUNPACK32, 8: CODEC_RUNPACK64,
-                16: CODEC_RUNPACK128}[width]
-    except (KeyError, TypeError):
-        raise ValueError(f"RUNPACK element width must be 1, 2, 4, 8 or 16, not {width!r}") from None
+    return _column_codec("RUNPACK", width)
 
 
 def codec_autopack(width):
     """the AUTOPACK codec id of an element width of 1, 2, 4, 8 or 16 bytes"""
-    try:
-        return {1: CODEC_AUTOPACK8, 2: CODEC_AUTOPACK16, 4: CODEC_AUTOPACK32, 8: CODEC_AUTOPACK64,
-                16: CODEC_AUTOPACK128}[width]
-    except (KeyError, TypeError):
-        raise ValueError(f"AUTOPACK element width must be 1, 2, 4, 8 or 16, not {width!r}") from None
+    return _column_codec("AUTOPACK", width)
 
 
 def max_distance(codec):
@@ -399,16 +398,16 @@ class Engine:
         empty streams and tags of no format}.  Reads the tag bytes only (a strided view of the
         slab on torch's current stream); waits for them."""
         t = self.torch
+        formats = {nibble: name for name, (_, nibble, _) in COLUMN_CODECS.items() if nibble}
         if nseg == 0:
-            return {k: 0 for k in ("INTPACK", "FLTPACK", "DICTPACK", "RUNPACK", "stored", "other")}
+            return {k: 0 for k in (*formats.values(), "stored", "other")}
         tags = t.as_strided(slab, (nseg,), (stride,)).to(t.int64)
         nib = tags >> 4
         live = sizes[:nseg] != 0
         # INTPACK and FLTPACK store with mode 2 in bits 2..3, DICTPACK and RUNPACK with bit 3
         stored = t.where(nib <= 5, (tags >> 2 & 3) == 2, (tags >> 3 & 1) == 1)
         known = live & (nib >= 4) & (nib <= 7)
-        out = {name: int((known & ~stored & (nib == k)).sum())
-               for k, name in ((4, "INTPACK"), (5, "FLTPACK"), (6, "DICTPACK"), (7, "RUNPACK"))}
+        out = {name: int((known & ~stored & (nib == k)).sum()) for k, name in formats.items()}
         out["stored"] = int((known & stored).sum())
         out["other"] = nseg - int(known.sum())
         return out

@@ -291,6 +291,38 @@ bool OnDevice(std::uint64_t address, int device) {
   return kind == 2 && dev == device;
 }
 
+// The column codecs (no matches: no window, no filter, no chained operations) and the element
+// widths each takes, ORed together.
+struct ColumnCodec {
+  Codec codec;
+  const char* name;
+  std::uint32_t widths;
+};
+constexpr ColumnCodec kColumnCodecs[] = {{Codec::INTPACK, "INTPACK", 1 | 2 | 4 | 8},
+                                         {Codec::FLTPACK, "FLTPACK", 4 | 8},
+                                         {Codec::DICTPACK, "DICTPACK", 4 | 8 | 16},
+                                         {Codec::RUNPACK, "RUNPACK", 1 | 2 | 4 | 8 | 16},
+                                         {Codec::AUTOPACK, "AUTOPACK", 1 | 2 | 4 | 8 | 16}};
+
+const ColumnCodec* FindColumnCodec(Codec codec) {
+  for (const auto& c : kColumnCodecs)
+    if (c.codec == codec) return &c;
+  return nullptr;
+}
+
+bool IsColumnCodec(Codec codec) { return FindColumnCodec(codec) != nullptr; }
+
+// "1, 2, 4 or 8" for 1 | 2 | 4 | 8
+std::string WidthList(std::uint32_t widths) {
+  std::string text;
+  for (std::uint32_t w = 1; w <= widths; w <<= 1) {
+    if (!(widths & w)) continue;
+    if (!text.empty()) text += widths >= 2 * w ? ", " : " or ";
+    text += std::to_string(w);
+  }
+  return text;
+}
+
 // DEFLATE + FIXED -> fixed-Huffman blocks; DEFLATE + DYNAMIC (the reference default,
 // config.h:151) or DEFAULT (the PMD's choice) -> dynamic Huffman
 // INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK -> the id of the configured element width
@@ -769,10 +801,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   if (configuration_->burst_size() == 0)
     return arrow::Status::Invalid("Burst size must be greater than 0");
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
-      configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::INTPACK &&
-      configuration_->codec() != Codec::FLTPACK && configuration_->codec() != Codec::DICTPACK &&
-      configuration_->codec() != Codec::RUNPACK && configuration_->codec() != Codec::AUTOPACK &&
-      configuration_->codec() != Codec::SNAPPY)
+      configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::SNAPPY &&
+      !internal::IsColumnCodec(configuration_->codec()))
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
   if (configuration_->max_sgl_segs() < 1) configuration_->set_max_sgl_segs(1);
@@ -788,45 +818,14 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
     return arrow::Status::Invalid("decompressed_seg_size is not in the range of [",
                                   internal::kMinSegSize, ", ", internal::kMaxSegSize32, "]");
   }
-  if (configuration_->codec() == Codec::INTPACK) {
+  if (const auto* column = internal::FindColumnCodec(configuration_->codec())) {
     const auto w = element_width();
-    if (w != 1 && w != 2 && w != 4 && w != 8)
-      return arrow::Status::Invalid("element_width (", w, ") of INTPACK must be 1, 2, 4 or 8");
+    if ((w & (w - 1)) != 0 || !(column->widths & w))
+      return arrow::Status::Invalid("element_width (", w, ") of ", column->name, " must be ",
+                                    internal::WidthList(column->widths));
     // (a chained op would be one stream over k slots: the codec has no use for it)
     if (configuration_->max_sgl_segs() > 1)
-      return arrow::Status::Invalid("INTPACK cannot be combined with chained operations "
-                                    "(max_sgl_segs > 1)");
-  }
-  if (configuration_->codec() == Codec::FLTPACK) {
-    const auto w = element_width();
-    if (w != 4 && w != 8)
-      return arrow::Status::Invalid("element_width (", w, ") of FLTPACK must be 4 or 8");
-    if (configuration_->max_sgl_segs() > 1)
-      return arrow::Status::Invalid("FLTPACK cannot be combined with chained operations "
-                                    "(max_sgl_segs > 1)");
-  }
-  if (configuration_->codec() == Codec::DICTPACK) {
-    const auto w = element_width();
-    if (w != 4 && w != 8 && w != 16)
-      return arrow::Status::Invalid("element_width (", w, ") of DICTPACK must be 4, 8 or 16");
-    if (configuration_->max_sgl_segs() > 1)
-      return arrow::Status::Invalid("DICTPACK cannot be combined with chained operations "
-                                    "(max_sgl_segs > 1)");
-  }
-  if (configuration_->codec() == Codec::RUNPACK) {
-    const auto w = element_width();
-    if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
-      return arrow::Status::Invalid("element_width (", w, ") of RUNPACK must be 1, 2, 4, 8 or 16");
-    if (configuration_->max_sgl_segs() > 1)
-      return arrow::Status::Invalid("RUNPACK cannot be combined with chained operations "
-                                    "(max_sgl_segs > 1)");
-  }
-  if (configuration_->codec() == Codec::AUTOPACK) {
-    const auto w = element_width();
-    if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16)
-      return arrow::Status::Invalid("element_width (", w, ") of AUTOPACK must be 1, 2, 4, 8 or 16");
-    if (configuration_->max_sgl_segs() > 1)
-      return arrow::Status::Invalid("AUTOPACK cannot be combined with chained operations "
+      return arrow::Status::Invalid(column->name, " cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
   }
   // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
@@ -848,10 +847,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   while ((1u << window) < reach) ++window;
   encoder_window_ = window;
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
-  if (configuration_->codec() == Codec::INTPACK || configuration_->codec() == Codec::FLTPACK ||
-      configuration_->codec() == Codec::DICTPACK ||
-      configuration_->codec() == Codec::RUNPACK ||
-      configuration_->codec() == Codec::AUTOPACK) {  // no matches, no window: ignored, reported 0
+  // (a column codec has no matches and no window: ignored, reported 0)
+  if (internal::IsColumnCodec(configuration_->codec())) {
     encoder_window_ = 0;
     configuration_->set_window_size(0);
   } else if (configuration_->window_size() == 0) {
@@ -906,16 +903,8 @@ arrow::Status HipCompressDevice::ValidateConfiguration() {
     if (hip_configuration->max_sgl_segs() > 1)
       return arrow::Status::Invalid("A filter cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
-    if (hip_configuration->codec() == Codec::INTPACK)
-      return arrow::Status::Invalid("INTPACK takes no filter");
-    if (hip_configuration->codec() == Codec::FLTPACK)
-      return arrow::Status::Invalid("FLTPACK takes no filter");
-    if (hip_configuration->codec() == Codec::DICTPACK)
-      return arrow::Status::Invalid("DICTPACK takes no filter");
-    if (hip_configuration->codec() == Codec::RUNPACK)
-      return arrow::Status::Invalid("RUNPACK takes no filter");
-    if (hip_configuration->codec() == Codec::AUTOPACK)
-      return arrow::Status::Invalid("AUTOPACK takes no filter");
+    if (const auto* column = internal::FindColumnCodec(hip_configuration->codec()))
+      return arrow::Status::Invalid(column->name, " takes no filter");
   }
   return HipGfx950CompressDevice::ValidateConfiguration();
 }

@@ -313,107 +313,37 @@ __device__ __forceinline__ bool decompress_packed(const GMEM uint8_t* src, uint3
 
 }  // namespace fpk
 
-// Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
-// or dsts[i]; any alignment); sizes[i] = the stream's size (at most 4 + the segment's length:
-// never a failure).
-template <uint32_t W>
-__global__ __launch_bounds__(64) void fltpack_compress_kernel(
-    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
-    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
-  __shared__ fpk::Shared sh;
-  const uint32_t i = blockIdx.x;
-  const uint64_t seg_off = (uint64_t)i * seg;
-  if (seg_off >= n_total) return;
-  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
-  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
-  fpk::compress_segment<W>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
-}
+// FLTPACK as the shared kernels see it (autopack.hip.h).  Slots have any alignment.
+struct FltPack {
+  static constexpr uint32_t kNibble = 5;
+  template <uint32_t W> using EncShared = fpk::Shared;
+  using DecShared = fpk::DecShared;
 
-template __global__ void fltpack_compress_kernel<4>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                                    uint64_t, uint8_t* const*, uint32_t*);
-template __global__ void fltpack_compress_kernel<8>(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                                    uint64_t, uint8_t* const*, uint32_t*);
+  template <uint32_t W, bool STORE>
+  static constexpr auto compress_segment = &fpk::compress_segment<W, STORE>;
 
-// The same, for a candidate of AUTOPACK: a segment that would be stored gets its size only.
-template <uint32_t W>
-__global__ __launch_bounds__(64) void fltpack_compress_candidate_kernel(
-    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
-    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
-  __shared__ fpk::Shared sh;
-  const uint32_t i = blockIdx.x;
-  const uint64_t seg_off = (uint64_t)i * seg;
-  if (seg_off >= n_total) return;
-  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
-  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
-  fpk::compress_segment<W, false>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
-}
-
-template __global__ void fltpack_compress_candidate_kernel<4>(const uint8_t*, uint64_t, uint32_t,
-    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
-template __global__ void fltpack_compress_candidate_kernel<8>(const uint8_t*, uint64_t, uint32_t,
-    uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
-
-// Segment i: csizes[i] bytes at srcs[i] (or slab + i*slot_stride) -> out + i*seg; produced[i] =
-// its length, or BITAR_HIP_SEGMENT_ERROR (and bit 0 of the error word) for a stream the format
-// rejects.  The element width comes from the stream's tag.  Nothing outside the stream's
-// csizes[i] bytes is used (an aligned dword is loaded only when one of its bytes is), and
-// nothing outside the segment's seg bytes is written.
-__device__ __forceinline__ void fltpack_decompress_segment(
-    uint32_t i, const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab,
-    uint64_t slot_stride, const uint32_t* __restrict__ csizes, uint32_t seg,
-    uint8_t* __restrict__ out, uint32_t* __restrict__ produced, uint32_t* __restrict__ err,
-    fpk::DecShared& sh) {
-  const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
-  GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
-  const uint32_t csize = csizes[i];
-  bool ok = csize >= 4;
-  uint32_t L = 0;
-  if (ok) {
-    const uint32_t tag = src[0], e = src[1];
+  static __device__ __forceinline__ bool decode_stream(const GMEM uint8_t* src, uint32_t csize,
+                                                       uint32_t tag, uint32_t e, uint32_t L,
+                                                       uint32_t seg, GMEM uint8_t* dst,
+                                                       DecShared& sh) {
     const uint32_t mode = (tag >> 2) & 3u, lg = tag & 3u;
-    L = 1u + src[2] + ((uint32_t)src[3] << 8);
-    ok = (tag >> 4) == 5u && (mode == 0u || mode == 2u) && lg >= 2u && e <= fpk::kMaxExp &&
-         L <= seg;
+    bool ok = (tag >> 4) == kNibble && (mode == 0u || mode == 2u) && lg >= 2u &&
+              e <= fpk::kMaxExp && L <= seg;
     if (ok && mode == 2) {
-      ok = e == 0 && csize == 4u + L;
-      if (ok) wave_copy_global(dst, src + 4, L);
+      ok = e == 0 && decode_stored(src, csize, L, dst);
     } else if (ok) {
       ok = lg == 2 ? fpk::decompress_packed<4>(src, csize, L, e, dst, sh)
                    : fpk::decompress_packed<8>(src, csize, L, e, dst, sh);
     }
+    return ok;
   }
-  if (lane_id() == 0) {
-    if (ok) {
-      produced[i] = L;
-    } else {
-      produced[i] = BITAR_HIP_SEGMENT_ERROR;
-      atomicOr(err, 1u);
-    }
-  }
-}
+};
 
-__global__ __launch_bounds__(64) void fltpack_decompress_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
-  __shared__ fpk::DecShared sh;
-  const uint32_t i = blockIdx.x;
-  if (i >= nseg) return;
-  fltpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
-}
-
-// AUTOPACK's decoder of this format (autopack.hip.h): a grid of nseg workgroups of which the
-// listed ones -- or, without a list, those whose stream carries this format's tag -- do exactly
-// what the kernel above does for their segment; the others leave at once and write nothing.
-__global__ __launch_bounds__(64) void fltpack_decompress_listed_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err, const uint32_t* __restrict__ list,
-    const uint32_t* __restrict__ count) {
-  __shared__ fpk::DecShared sh;
-  const uint32_t i = listed_segment(5u, list, count, srcs, slab, slot_stride, csizes, nseg);
-  if (i == kNoSegment) return;
-  fltpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
-}
+BITAR_COLUMN_COMPRESS(FltPack, 4, true);
+BITAR_COLUMN_COMPRESS(FltPack, 8, true);
+BITAR_COLUMN_COMPRESS(FltPack, 4, false);
+BITAR_COLUMN_COMPRESS(FltPack, 8, false);
+BITAR_COLUMN_DECOMPRESS(FltPack, false);
+BITAR_COLUMN_DECOMPRESS(FltPack, true);
 
 }  // namespace bitar_hip

@@ -498,56 +498,26 @@ __device__ __forceinline__ bool decompress_runs(const GMEM uint8_t* src, uint32_
 
 }  // namespace rpk
 
-// Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
-// or dsts[i]); sizes[i] = the stream's size (at most 4 + the segment's length: never a failure).
-// Nothing at or past that size is written in the slot.
-template <uint32_t W>
-__global__ __launch_bounds__(64) void runpack_compress_kernel(
-    const uint8_t* __restrict__ input, uint64_t n_total, uint32_t seg, uint8_t* __restrict__ slab,
-    uint64_t slot_stride, uint8_t* const* __restrict__ dsts, uint32_t* __restrict__ sizes) {
-  __shared__ rpk::EncShared<W> sh;
-  const uint32_t i = blockIdx.x;
-  const uint64_t seg_off = (uint64_t)i * seg;
-  if (seg_off >= n_total) return;
-  const uint32_t L = (uint32_t)(n_total - seg_off < seg ? n_total - seg_off : seg);
-  GMEM uint8_t* dst = global_ptr(dsts ? dsts[i] : slab + (uint64_t)i * slot_stride);
-  rpk::compress_segment<W>(global_ptr(input + seg_off), L, dst, sizes + i, sh);
-}
+// RUNPACK as the shared kernels see it (autopack.hip.h).  The encoder writes nothing at or past
+// the stream's size in its slot, and it has the storing form alone: as AUTOPACK's first candidate
+// it writes into the caller's slot.  The decoder leaves a rejected segment's output range
+// untouched and writes nothing outside the segment's first L bytes.
+struct RunPack {
+  static constexpr uint32_t kNibble = 7;
+  template <uint32_t W> using EncShared = rpk::EncShared<W>;
+  using DecShared = rpk::DecShared;
 
-#define BITAR_RUNPACK_INSTANCE(W)                                                              \
-  template __global__ void runpack_compress_kernel<W>(const uint8_t*, uint64_t, uint32_t,      \
-                                                      uint8_t*, uint64_t, uint8_t* const*,     \
-                                                      uint32_t*)
-BITAR_RUNPACK_INSTANCE(1);
-BITAR_RUNPACK_INSTANCE(2);
-BITAR_RUNPACK_INSTANCE(4);
-BITAR_RUNPACK_INSTANCE(8);
-BITAR_RUNPACK_INSTANCE(16);
-#undef BITAR_RUNPACK_INSTANCE
+  template <uint32_t W, bool STORE>
+  static constexpr auto compress_segment = &rpk::compress_segment<W>;  // (STORE alone)
 
-// Segment i: csizes[i] bytes at srcs[i] (or slab + i*slot_stride) -> out + i*seg; produced[i] =
-// its length, or BITAR_HIP_SEGMENT_ERROR (and bit 0 of the error word) for a stream the format
-// rejects: such a segment's output range is left untouched.  The element width comes from the
-// stream's tag.  Nothing outside the stream's csizes[i] bytes is used (an aligned dword is loaded
-// only when one of its bytes is), and nothing outside the segment's first L bytes is written.
-__device__ __forceinline__ void runpack_decompress_segment(
-    uint32_t i, const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab,
-    uint64_t slot_stride, const uint32_t* __restrict__ csizes, uint32_t seg,
-    uint8_t* __restrict__ out, uint32_t* __restrict__ produced, uint32_t* __restrict__ err,
-    rpk::DecShared& sh) {
-  const GMEM uint8_t* src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
-  GMEM uint8_t* dst = global_ptr(out + (uint64_t)i * seg);
-  const uint32_t csize = csizes[i];
-  bool ok = csize >= 4;
-  uint32_t L = 0;
-  if (ok) {
-    const uint32_t tag = src[0], bl = src[1];
+  static __device__ __forceinline__ bool decode_stream(const GMEM uint8_t* src, uint32_t csize,
+                                                       uint32_t tag, uint32_t bl, uint32_t L,
+                                                       uint32_t seg, GMEM uint8_t* dst,
+                                                       DecShared& sh) {
     const uint32_t lg = tag & 7u;
-    L = 1u + src[2] + ((uint32_t)src[3] << 8);
-    ok = (tag >> 4) == 7u && lg <= 4u && L <= seg;
+    bool ok = (tag >> 4) == kNibble && lg <= 4u && L <= seg;
     if (ok && (tag & 8u)) {
-      ok = bl == 0 && csize == 4u + L;
-      if (ok) wave_copy_global(dst, src + 4, L);
+      ok = bl == 0 && decode_stored(src, csize, L, dst);
     } else if (ok) {
       switch (lg) {
         case 0: ok = rpk::decompress_runs<1>(src, csize, bl, L, dst, sh); break;
@@ -557,39 +527,16 @@ __device__ __forceinline__ void runpack_decompress_segment(
         default: ok = rpk::decompress_runs<16>(src, csize, bl, L, dst, sh); break;
       }
     }
+    return ok;
   }
-  if (lane_id() == 0) {
-    if (ok) {
-      produced[i] = L;
-    } else {
-      produced[i] = BITAR_HIP_SEGMENT_ERROR;
-      atomicOr(err, 1u);
-    }
-  }
-}
+};
 
-__global__ __launch_bounds__(64) void runpack_decompress_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err) {
-  __shared__ rpk::DecShared sh;
-  const uint32_t i = blockIdx.x;
-  if (i >= nseg) return;
-  runpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
-}
-
-// AUTOPACK's decoder of this format (autopack.hip.h): a grid of nseg workgroups of which the
-// listed ones -- or, without a list, those whose stream carries this format's tag -- do exactly
-// what the kernel above does for their segment; the others leave at once and write nothing.
-__global__ __launch_bounds__(64) void runpack_decompress_listed_kernel(
-    const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab, uint64_t slot_stride,
-    const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg, uint8_t* __restrict__ out,
-    uint32_t* __restrict__ produced, uint32_t* __restrict__ err, const uint32_t* __restrict__ list,
-    const uint32_t* __restrict__ count) {
-  __shared__ rpk::DecShared sh;
-  const uint32_t i = listed_segment(7u, list, count, srcs, slab, slot_stride, csizes, nseg);
-  if (i == kNoSegment) return;
-  runpack_decompress_segment(i, srcs, slab, slot_stride, csizes, seg, out, produced, err, sh);
-}
+BITAR_COLUMN_COMPRESS(RunPack, 1, true);
+BITAR_COLUMN_COMPRESS(RunPack, 2, true);
+BITAR_COLUMN_COMPRESS(RunPack, 4, true);
+BITAR_COLUMN_COMPRESS(RunPack, 8, true);
+BITAR_COLUMN_COMPRESS(RunPack, 16, true);
+BITAR_COLUMN_DECOMPRESS(RunPack, false);
+BITAR_COLUMN_DECOMPRESS(RunPack, true);
 
 }  // namespace bitar_hip

@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "../../include/bitar_hip.h"
+#define BITAR_COLUMN_DECLARATIONS_ONLY  // (the kernels are defined in the formats' files)
+#include "autopack.hip.h"
 #include "order.hip.h"
 #include "zstd_hand.hip.h"
 #include "zstd_layout.hip.h"
@@ -100,47 +102,6 @@ __global__ void checksum_kernel(uint32_t, const uint8_t*, uint64_t, uint32_t, co
 template <uint32_t W, bool BITS, bool INV>
 __global__ void filter_kernel(const uint8_t*, uint64_t, uint32_t, const uint32_t*, uint32_t,
                               uint8_t*);
-template <uint32_t W>
-__global__ void intpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                        uint8_t* const*, uint32_t*);
-__global__ void intpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                          uint32_t*);
-template <uint32_t W>
-__global__ void fltpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                        uint8_t* const*, uint32_t*);
-__global__ void fltpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                          uint32_t*);
-template <uint32_t W>
-__global__ void dictpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                         uint8_t* const*, uint32_t*);
-__global__ void dictpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                           const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                           uint32_t*);
-template <uint32_t W>
-__global__ void runpack_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                        uint8_t* const*, uint32_t*);
-__global__ void runpack_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                          uint32_t*);
-template <uint32_t W>
-__global__ void intpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                                  uint64_t, uint8_t* const*, uint32_t*);
-template <uint32_t W>
-__global__ void fltpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                                  uint64_t, uint8_t* const*, uint32_t*);
-template <uint32_t W>
-__global__ void dictpack_compress_candidate_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                                   uint64_t, uint8_t* const*, uint32_t*);
-#define BITAR_LISTED_DECODER(name)                                                           \
-  __global__ void name(const uint8_t* const*, const uint8_t*, uint64_t, const uint32_t*, uint32_t, \
-                       uint32_t, uint8_t*, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*)
-BITAR_LISTED_DECODER(intpack_decompress_listed_kernel);
-BITAR_LISTED_DECODER(fltpack_decompress_listed_kernel);
-BITAR_LISTED_DECODER(dictpack_decompress_listed_kernel);
-BITAR_LISTED_DECODER(runpack_decompress_listed_kernel);
-#undef BITAR_LISTED_DECODER
 __global__ void autopack_select_kernel(const uint8_t*, uint64_t, const uint32_t*, uint32_t, uint32_t,
                                        uint32_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
 __global__ void autopack_route_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
@@ -391,30 +352,88 @@ int bitar_hip_device(bitar_hip_ctx* ctx, int* device) {
   return 0;
 }
 
-// the four INTPACK ids, 8 + log2 of the element width
-static bool is_intpack(uint32_t codec) {
-  return codec >= BITAR_HIP_CODEC_INTPACK8 && codec <= BITAR_HIP_CODEC_INTPACK64;
+extern "C++" {
+// The column codecs: a family's ids are base + log2(element width) for the widths it offers
+// (`widths`: those widths ORed together, so bit lg stands for 1 << lg bytes), and its streams
+// carry `nibble` in the high half of byte 0
+// (AUTOPACK has no format of its own).  Two orders here are load-bearing:
+//   Candidate order (AUTOPACK compress): RUNPACK first, into the caller's slot; then INTPACK,
+//     DICTPACK, FLTPACK into scratch slabs k = 0, 1, 2.  autopack_select_kernel breaks ties
+//     towards the earlier candidate.
+//   Listed-decoder order (AUTOPACK decompress): list f belongs to family f of this table, tag
+//     nibble 4 + f -- INTPACK, FLTPACK, DICTPACK, RUNPACK -- which is what autopack_route_kernel
+//     writes.
+enum ColumnFamily : int { kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kColumnFamilies };
+struct ColumnRow {
+  uint32_t base, nibble, widths;
+};
+constexpr ColumnRow kColumn[kColumnFamilies] = {
+    {BITAR_HIP_CODEC_INTPACK8, 4, 1 | 2 | 4 | 8},            // INTPACK
+    {BITAR_HIP_CODEC_FLTPACK32 - 2, 5, 4 | 8},               // FLTPACK
+    {BITAR_HIP_CODEC_DICTPACK32 - 2, 6, 4 | 8 | 16},         // DICTPACK
+    {BITAR_HIP_CODEC_RUNPACK8, 7, 1 | 2 | 4 | 8 | 16},       // RUNPACK
+    {BITAR_HIP_CODEC_AUTOPACK8, 0, 1 | 2 | 4 | 8 | 16},      // AUTOPACK
+};
+constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
+constexpr uint32_t kListedDecoders = 4;
+static_assert(kColumn[kIntPack].nibble == 4 && kColumn[kFltPack].nibble == 5 &&
+                  kColumn[kDictPack].nibble == 6 && kColumn[kRunPack].nibble == 7,
+              "list f is tag nibble 4 + f");
+
+static bool offers(ColumnFamily f, uint32_t lg) { return lg < 5 && (kColumn[f].widths >> lg & 1u); }
+
+// codec -> its family and log2 of its element width; family kColumnFamilies: not a column codec
+struct ColumnCodec {
+  ColumnFamily family;
+  uint32_t lg;
+  explicit operator bool() const { return family != kColumnFamilies; }
+};
+static ColumnCodec column_codec(uint32_t codec) {
+  for (int f = 0; f < kColumnFamilies; ++f)
+    if (offers((ColumnFamily)f, codec - kColumn[f].base))
+      return {(ColumnFamily)f, codec - kColumn[f].base};
+  return {kColumnFamilies, 0};
 }
 
-// the two FLTPACK ids, 16 + log2 of the element width
-static bool is_fltpack(uint32_t codec) {
-  return codec == BITAR_HIP_CODEC_FLTPACK32 || codec == BITAR_HIP_CODEC_FLTPACK64;
+// The kernels of a family (not AUTOPACK) at a width it offers: the one place where a run-time
+// width becomes a template argument.  Only instantiations the formats' files define are named.
+using CompressKernel = void (*)(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
+                                uint8_t* const*, uint32_t*);
+using DecompressKernel = void (*)(const uint8_t* const*, const uint8_t*, uint64_t, const uint32_t*,
+                                  uint32_t, uint32_t, uint8_t*, uint32_t*, uint32_t*,
+                                  const uint32_t*, const uint32_t*);
+template <class F, ColumnFamily FAMILY, bool STORE, uint32_t LG = 0>
+static CompressKernel width_kernel(uint32_t lg) {
+  if constexpr (LG < 5) {
+    if constexpr ((kColumn[FAMILY].widths >> LG & 1u) != 0)
+      if (lg == LG) return bitar_hip::column_compress_kernel<F, 1u << LG, STORE>;
+    return width_kernel<F, FAMILY, STORE, LG + 1>(lg);
+  } else {
+    return nullptr;
+  }
 }
-
-// the three DICTPACK ids, 24 + log2 of the element width (4, 8 or 16 bytes)
-static bool is_dictpack(uint32_t codec) {
-  return codec >= BITAR_HIP_CODEC_DICTPACK32 && codec <= BITAR_HIP_CODEC_DICTPACK128;
+// STORE = false: the store-less form of a later candidate of AUTOPACK (RUNPACK, always the
+// first, has none)
+template <bool STORE>
+static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
+  switch (f) {
+    case kIntPack: return width_kernel<bitar_hip::IntPack, kIntPack, STORE>(lg);
+    case kFltPack: return width_kernel<bitar_hip::FltPack, kFltPack, STORE>(lg);
+    case kDictPack: return width_kernel<bitar_hip::DictPack, kDictPack, STORE>(lg);
+    case kRunPack: return width_kernel<bitar_hip::RunPack, kRunPack, true>(lg);
+    default: return nullptr;
+  }
 }
-
-// the five RUNPACK ids, 32 + log2 of the element width (1, 2, 4, 8 or 16 bytes)
-static bool is_runpack(uint32_t codec) {
-  return codec >= BITAR_HIP_CODEC_RUNPACK8 && codec <= BITAR_HIP_CODEC_RUNPACK128;
+template <bool LISTED>
+static DecompressKernel decompress_kernel(uint32_t f) {
+  switch (f) {
+    case kIntPack: return bitar_hip::column_decompress_kernel<bitar_hip::IntPack, LISTED>;
+    case kFltPack: return bitar_hip::column_decompress_kernel<bitar_hip::FltPack, LISTED>;
+    case kDictPack: return bitar_hip::column_decompress_kernel<bitar_hip::DictPack, LISTED>;
+    default: return bitar_hip::column_decompress_kernel<bitar_hip::RunPack, LISTED>;
+  }
 }
-
-// the five AUTOPACK ids, 40 + log2 of the element width (1, 2, 4, 8 or 16 bytes)
-static bool is_autopack(uint32_t codec) {
-  return codec >= BITAR_HIP_CODEC_AUTOPACK8 && codec <= BITAR_HIP_CODEC_AUTOPACK128;
-}
+}  // extern "C++"
 
 // AUTOPACK decode: 1 (default) sorts the segments into one index list per format on the device,
 // 0 has every format's decoder look at every segment's tag (DESIGN.md 4.21 has both measured).
@@ -433,8 +452,7 @@ static bool autopack_storeless() {
 
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
   uint64_t bound;
-  if (is_intpack(codec) || is_fltpack(codec) || is_dictpack(codec) || is_runpack(codec) ||
-      is_autopack(codec))
+  if (column_codec(codec))
     bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
   else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
@@ -460,26 +478,8 @@ uint32_t bitar_hip_max_distance(uint32_t codec) {
     case BITAR_HIP_CODEC_DEFLATE_DYNAMIC:
     case BITAR_HIP_CODEC_ZSTD: return 4096u - 1536u;
     case BITAR_HIP_CODEC_LZ4_WIDE: return 16384u - 1536u;
-    case BITAR_HIP_CODEC_INTPACK8:
-    case BITAR_HIP_CODEC_INTPACK16:
-    case BITAR_HIP_CODEC_INTPACK32:
-    case BITAR_HIP_CODEC_INTPACK64:
-    case BITAR_HIP_CODEC_FLTPACK32:
-    case BITAR_HIP_CODEC_FLTPACK64:
-    case BITAR_HIP_CODEC_DICTPACK32:
-    case BITAR_HIP_CODEC_DICTPACK64:
-    case BITAR_HIP_CODEC_DICTPACK128:
-    case BITAR_HIP_CODEC_RUNPACK8:
-    case BITAR_HIP_CODEC_RUNPACK16:
-    case BITAR_HIP_CODEC_RUNPACK32:
-    case BITAR_HIP_CODEC_RUNPACK64:
-    case BITAR_HIP_CODEC_RUNPACK128:
-    case BITAR_HIP_CODEC_AUTOPACK8:
-    case BITAR_HIP_CODEC_AUTOPACK16:
-    case BITAR_HIP_CODEC_AUTOPACK32:
-    case BITAR_HIP_CODEC_AUTOPACK64:
-    case BITAR_HIP_CODEC_AUTOPACK128: return 0;  // "none": the codec has no matches at all
-    default: return 0;                          // "unknown": no such codec
+    // a column codec: "none", it has no matches at all; any other id: "unknown", no such codec
+    default: return 0;
   }
 }
 
@@ -615,8 +615,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
       codec != BITAR_HIP_CODEC_LZ4_WIDE && codec != BITAR_HIP_CODEC_SNAPPY &&
-      !is_intpack(codec) && !is_fltpack(codec) &&
-      !is_dictpack(codec) && !is_runpack(codec) && !is_autopack(codec))
+      !column_codec(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -640,59 +639,23 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
                          cin, nb, seg, cn, keys);
     });
   };
-  if (is_intpack(codec)) {
-    // one streaming kernel, the same work for every segment: plain order (intpack.hip)
-#define BITAR_INTPACK(W)                                                                      \
-  hipLaunchKernelGGL(bitar_hip::intpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, s, \
-                     in, n, seg, slab, slot_stride, dsts, d_sizes)
-    if (codec == BITAR_HIP_CODEC_INTPACK8) BITAR_INTPACK(1);
-    else if (codec == BITAR_HIP_CODEC_INTPACK16) BITAR_INTPACK(2);
-    else if (codec == BITAR_HIP_CODEC_INTPACK32) BITAR_INTPACK(4);
-    else BITAR_INTPACK(8);
-#undef BITAR_INTPACK
+  const ColumnCodec cc = column_codec(codec);
+  if (cc && cc.family != kAutoPack) {
+    // one streaming kernel, the same work for every segment: plain order (intpack.hip,
+    // fltpack.hip, dictpack.hip, runpack.hip)
+    hipLaunchKernelGGL(compress_kernel<true>(cc.family, cc.lg), dim3((uint32_t)nseg), dim3(64), 0,
+                       s, in, n, seg, slab, slot_stride, dsts, d_sizes);
   }
-  else if (is_fltpack(codec)) {
-    // the same shape: one streaming kernel in plain order (fltpack.hip)
-    if (codec == BITAR_HIP_CODEC_FLTPACK32)
-      hipLaunchKernelGGL(bitar_hip::fltpack_compress_kernel<4>, dim3((uint32_t)nseg), dim3(64), 0,
-                         s, in, n, seg, slab, slot_stride, dsts, d_sizes);
-    else
-      hipLaunchKernelGGL(bitar_hip::fltpack_compress_kernel<8>, dim3((uint32_t)nseg), dim3(64), 0,
-                         s, in, n, seg, slab, slot_stride, dsts, d_sizes);
-  }
-  else if (is_dictpack(codec)) {
-    // likewise (dictpack.hip)
-#define BITAR_DICTPACK(W)                                                                      \
-  hipLaunchKernelGGL(bitar_hip::dictpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, \
-                     s, in, n, seg, slab, slot_stride, dsts, d_sizes)
-    if (codec == BITAR_HIP_CODEC_DICTPACK32) BITAR_DICTPACK(4);
-    else if (codec == BITAR_HIP_CODEC_DICTPACK64) BITAR_DICTPACK(8);
-    else BITAR_DICTPACK(16);
-#undef BITAR_DICTPACK
-  }
-  else if (is_runpack(codec)) {
-    // likewise (runpack.hip)
-#define BITAR_RUNPACK(W)                                                                      \
-  hipLaunchKernelGGL(bitar_hip::runpack_compress_kernel<W>, dim3((uint32_t)nseg), dim3(64), 0, \
-                     s, in, n, seg, slab, slot_stride, dsts, d_sizes)
-    switch (codec) {
-      case BITAR_HIP_CODEC_RUNPACK8: BITAR_RUNPACK(1); break;
-      case BITAR_HIP_CODEC_RUNPACK16: BITAR_RUNPACK(2); break;
-      case BITAR_HIP_CODEC_RUNPACK32: BITAR_RUNPACK(4); break;
-      case BITAR_HIP_CODEC_RUNPACK64: BITAR_RUNPACK(8); break;
-      default: BITAR_RUNPACK(16); break;
-    }
-#undef BITAR_RUNPACK
-  }
-  else if (is_autopack(codec)) {
+  else if (cc) {
     // the smallest of the candidates' streams per segment (autopack.hip): RUNPACK straight
-    // into the caller's slots, every later candidate (INTPACK for 1- to 8-byte elements,
-    // DICTPACK for 4 to 16, FLTPACK for 4 and 8) into a stream-ordered scratch slab of its own
+    // into the caller's slots, every later candidate that offers the width (kCandidates,
+    // kColumn) into a stream-ordered scratch slab of its own
     // with its own sizes (store-less: a segment a later candidate would store gets its size
     // only, and the select kernel never takes it), then the select kernel.  Chunks of <=
     // kAutoChunkSegs segments over one allocation.
-    const uint32_t lg = codec - BITAR_HIP_CODEC_AUTOPACK8, w = 1u << lg;
-    const uint32_t extra = (w <= 8 ? 1u : 0u) + (w >= 4 ? 1u : 0u) + (w == 4 || w == 8 ? 1u : 0u);
+    uint32_t extra = 0;  // the candidates after the first
+    for (ColumnFamily f : kCandidates) extra += offers(f, cc.lg) ? 1u : 0u;
+    --extra;
     const uint64_t scr_stride = bitar_hip_slot_size(codec, seg);
     const Chunks ch(nseg, kAutoChunkSegs);
     const bool lean = autopack_storeless();
@@ -707,47 +670,20 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
       uint8_t* const* cdsts = dsts ? dsts + c0 : nullptr;
       const uint8_t* cin = in + cb;
       uint32_t k = 0;  // the next scratch candidate
-#define BITAR_CANDIDATE(kernel, W, to_slab, to_stride, to_dsts, to_sizes)                        \
-  hipLaunchKernelGGL(bitar_hip::kernel<W>, dim3(cn), dim3(64), 0, s, cin, nb, seg, to_slab,      \
-                     to_stride, to_dsts, to_sizes)
-#define BITAR_SCRATCH_CANDIDATE(name, W)                                                         \
-  do {                                                                                           \
-    if (lean)                                                                                    \
-      BITAR_CANDIDATE(name##_compress_candidate_kernel, W, scr + k * ch.size * scr_stride,       \
-                      scr_stride, (uint8_t* const*)nullptr, ssz + k * ch.size);                  \
-    else                                                                                         \
-      BITAR_CANDIDATE(name##_compress_kernel, W, scr + k * ch.size * scr_stride, scr_stride,     \
-                      (uint8_t* const*)nullptr, ssz + k * ch.size);                              \
-    ++k;                                                                                         \
-  } while (0)
-      switch (w) {
-        case 1:
-          BITAR_CANDIDATE(runpack_compress_kernel, 1, cslab, slot_stride, cdsts, d_sizes + c0);
-          BITAR_SCRATCH_CANDIDATE(intpack, 1);
-          break;
-        case 2:
-          BITAR_CANDIDATE(runpack_compress_kernel, 2, cslab, slot_stride, cdsts, d_sizes + c0);
-          BITAR_SCRATCH_CANDIDATE(intpack, 2);
-          break;
-        case 4:
-          BITAR_CANDIDATE(runpack_compress_kernel, 4, cslab, slot_stride, cdsts, d_sizes + c0);
-          BITAR_SCRATCH_CANDIDATE(intpack, 4);
-          BITAR_SCRATCH_CANDIDATE(dictpack, 4);
-          BITAR_SCRATCH_CANDIDATE(fltpack, 4);
-          break;
-        case 8:
-          BITAR_CANDIDATE(runpack_compress_kernel, 8, cslab, slot_stride, cdsts, d_sizes + c0);
-          BITAR_SCRATCH_CANDIDATE(intpack, 8);
-          BITAR_SCRATCH_CANDIDATE(dictpack, 8);
-          BITAR_SCRATCH_CANDIDATE(fltpack, 8);
-          break;
-        default:
-          BITAR_CANDIDATE(runpack_compress_kernel, 16, cslab, slot_stride, cdsts, d_sizes + c0);
-          BITAR_SCRATCH_CANDIDATE(dictpack, 16);
-          break;
+      for (ColumnFamily f : kCandidates) {
+        if (!offers(f, cc.lg)) continue;
+        if (f == kCandidates[0]) {
+          hipLaunchKernelGGL(compress_kernel<true>(f, cc.lg), dim3(cn), dim3(64), 0, s, cin, nb,
+                             seg, cslab, slot_stride, cdsts, d_sizes + c0);
+        } else {
+          const CompressKernel kernel =
+              lean ? compress_kernel<false>(f, cc.lg) : compress_kernel<true>(f, cc.lg);
+          hipLaunchKernelGGL(kernel, dim3(cn), dim3(64), 0, s, cin, nb, seg,
+                             scr + k * ch.size * scr_stride, scr_stride,
+                             (uint8_t* const*)nullptr, ssz + k * ch.size);
+          ++k;
+        }
       }
-#undef BITAR_SCRATCH_CANDIDATE
-#undef BITAR_CANDIDATE
       hipLaunchKernelGGL(bitar_hip::autopack_select_kernel, dim3((cn + 3) / 4), dim3(256), 0, s,
                          static_cast<const uint8_t*>(scr), scr_stride,
                          static_cast<const uint32_t*>(ssz), (uint32_t)ch.size, extra + 1u, cn,
@@ -1122,13 +1058,9 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const bool fixed_hint = codec == BITAR_HIP_CODEC_DEFLATE;
   if (codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC) codec = BITAR_HIP_CODEC_DEFLATE;  // same format
   if (codec == BITAR_HIP_CODEC_LZ4_WIDE) codec = BITAR_HIP_CODEC_LZ4;              // same format
-  if (is_intpack(codec)) codec = BITAR_HIP_CODEC_INTPACK8;  // (the width is in each stream's tag)
-  if (is_fltpack(codec)) codec = BITAR_HIP_CODEC_FLTPACK32;  // (likewise)
-  if (is_dictpack(codec)) codec = BITAR_HIP_CODEC_DICTPACK32;  // (likewise)
-  if (is_runpack(codec)) codec = BITAR_HIP_CODEC_RUNPACK8;  // (likewise)
-  if (is_autopack(codec)) codec = BITAR_HIP_CODEC_AUTOPACK8;  // (the format too)
-  if (codec != BITAR_HIP_CODEC_AUTOPACK8 && codec != BITAR_HIP_CODEC_INTPACK8 && codec != BITAR_HIP_CODEC_FLTPACK32 &&
-      codec != BITAR_HIP_CODEC_DICTPACK32 && codec != BITAR_HIP_CODEC_RUNPACK8 &&
+  // (a column codec's width is in each stream's tag, and under AUTOPACK the format too)
+  const ColumnCodec cc = column_codec(codec);
+  if (!cc &&
       codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_SNAPPY &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
@@ -1150,23 +1082,12 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const auto* srcs = reinterpret_cast<const uint8_t* const*>(d_srcs);
   const auto* slab = static_cast<const uint8_t*>(d_slab);
   auto* out = static_cast<uint8_t*>(d_out);
-  if (codec == BITAR_HIP_CODEC_INTPACK8) {
-    hipLaunchKernelGGL(bitar_hip::intpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
+  if (cc && cc.family != kAutoPack) {
+    hipLaunchKernelGGL(decompress_kernel<false>(cc.family), dim3(nseg), dim3(64), 0, s, srcs, slab,
+                       stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr);
   }
-  else if (codec == BITAR_HIP_CODEC_FLTPACK32) {
-    hipLaunchKernelGGL(bitar_hip::fltpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
-  }
-  else if (codec == BITAR_HIP_CODEC_DICTPACK32) {
-    hipLaunchKernelGGL(bitar_hip::dictpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
-  }
-  else if (codec == BITAR_HIP_CODEC_RUNPACK8) {
-    hipLaunchKernelGGL(bitar_hip::runpack_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s));
-  }
-  else if (codec == BITAR_HIP_CODEC_AUTOPACK8) {
+  else if (cc) {
     // each segment to the decoder its tag names (autopack.hip): the route kernel rejects the
     // segments no format claims and sorts the others into one index list per format, with the
     // counts, in a stream-ordered scratch; each format's listed decoder then runs over nseg
@@ -1190,15 +1111,11 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
       if (me != hipSuccess) break;
       hipLaunchKernelGGL(bitar_hip::autopack_route_kernel, dim3((cn + 255) / 256), dim3(256), 0, s,
                          csrcs, cslab, stride, csz, cn, cprod, ew, cl, counts);
-#define BITAR_LISTED(kernel, f)                                                                 \
-  hipLaunchKernelGGL(bitar_hip::kernel, dim3(cn), dim3(64), 0, s, csrcs, cslab, stride, csz, cn, \
-                     seg, cout, cprod, ew, lists ? cl + (uint64_t)(f)*cn : nullptr,             \
-                     lists ? counts + (f) : nullptr)
-      BITAR_LISTED(intpack_decompress_listed_kernel, 0);
-      BITAR_LISTED(fltpack_decompress_listed_kernel, 1);
-      BITAR_LISTED(dictpack_decompress_listed_kernel, 2);
-      BITAR_LISTED(runpack_decompress_listed_kernel, 3);
-#undef BITAR_LISTED
+      for (uint32_t f = 0; f < kListedDecoders; ++f)
+        hipLaunchKernelGGL(decompress_kernel<true>(f), dim3(cn), dim3(64), 0, s, csrcs, cslab,
+                           stride, csz, cn, seg, cout, cprod, ew,
+                           lists ? cl + (uint64_t)f * cn : (const uint32_t*)nullptr,
+                           lists ? counts + f : (const uint32_t*)nullptr);
     }
     const hipError_t le = hipGetLastError();
     if (scratch) HIP_TRY(hipFreeAsync(scratch, s), "scratch release");

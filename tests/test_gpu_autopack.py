@@ -126,6 +126,16 @@ def test_exact_bytes_and_round_trip(eng, w, seg):
             check_case(eng, w, seg, rnd(n, n))
 
 
+@pytest.mark.parametrize("knob", ("BITAR_HIP_AUTOPACK_LISTS", "BITAR_HIP_AUTOPACK_STORELESS"))
+@pytest.mark.parametrize("w", M.WIDTHS)
+def test_knobs_off_give_the_same_bytes(eng, w, knob, monkeypatch):
+    """the tag-peek decoders (LISTS=0) and the later candidates' storing kernels (STORELESS=0):
+    the library reads either variable at every call"""
+    monkeypatch.setenv(knob, "0")
+    for seg in (4096, 72):
+        check_case(eng, w, seg, C.stretches(w, seg))
+
+
 def test_ties_go_to_the_earlier_candidate(eng):
     a = np.full(129, 0xAB, np.uint8)          # w = 1: RUNPACK = INTPACK = 8
     (s,) = check_case(eng, 1, 4096, a)
