@@ -42,6 +42,11 @@ SEGMENT_ERROR = 0xFFFFFFFF
 CHECKSUM_CRC32, CHECKSUM_ADLER32, CHECKSUM_CRC32_ADLER32 = 1, 2, 3
 MAX_SEG_SIZE = 65536
 FILTER_SHUFFLE, FILTER_BITSHUFFLE = 1, 2  # bitar_hip_filter (element widths 2, 4, 8, 16)
+# whole-buffer raw Snappy streams (include/bitar_hip_snappy.h): the fragment size,
+# bitar_hip_snappy_split_status, and the bit of max_rounds that forbids the serial finish
+SNAPPY_BLOCK = 65536
+SNAPPY_SPLIT_OK, SNAPPY_SPLIT_UNSUPPORTED, SNAPPY_SPLIT_INVALID, SNAPPY_SPLIT_INCOMPLETE = range(4)
+SNAPPY_NO_SERIAL_FINISH = 0x80000000
 # bitar_hip_config.flags (initial decoder options of a context)
 FLAG_INFLATE_WAVE_ONLY, FLAG_ZSTD_WAVE_ONLY, FLAG_ZSTD_LANE_EXEC, FLAG_COUNT_PATHS = 1, 2, 4, 8
 FLAG_PLAIN_ORDER = 0x10  # segment i is workgroup i (no cost-ordered dispatch; same output)
@@ -128,6 +133,9 @@ def lib():
         "bitar_hip_crc32_combine": (i32, [vp, vp, vp, u64, u32, u32, vp]),
         "bitar_hip_filter_apply": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
         "bitar_hip_filter_invert": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
+        "bitar_hip_snappy_join": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp]),
+        "bitar_hip_snappy_split": (i32, [vp, vp, vp, u64, u64, u32, vp, vp, vp]),
+        "bitar_hip_snappy_decompress_joined": (i32, [vp, vp, vp, u64, u64, vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -151,6 +159,10 @@ ABI_SYMBOLS = ("bitar_hip_abi_version", "bitar_hip_last_error", "bitar_hip_devic
                "bitar_hip_compress_host", "bitar_hip_decompress_host",
                "bitar_hip_compress_bits", "bitar_hip_deflate_join", "bitar_hip_deflate_split",
                "bitar_hip_crc32_combine", "bitar_hip_filter_apply", "bitar_hip_filter_invert")
+# every symbol include/bitar_hip_snappy.h declares (whole-buffer raw Snappy streams: additive, a
+# header of their own; checked by tests/test_gpu_snappy_codec.py)
+SNAPPY_STREAM_SYMBOLS = ("bitar_hip_snappy_join", "bitar_hip_snappy_split",
+                         "bitar_hip_snappy_decompress_joined")
 
 
 def check(rc):
@@ -386,6 +398,36 @@ class Engine:
         """crc (int32 tensor, 1 entry) = CRC-32 of n bytes from their segments' CRC-32s"""
         check(lib().bitar_hip_crc32_combine(self.ctx, self._stream(stream), _ptr(sums), n, seg,
                                             (n + seg - 1) // seg, _ptr(crc)))
+
+    # --- one raw Snappy stream from the segments' streams, and back (DESIGN.md 4.23) -------
+    def snappy_join(self, slab, stride, sizes, n, offsets, joined=None, capacity=None,
+                    joined_len=None, seg=SNAPPY_BLOCK, stream=None):
+        """the slots of a CODEC_SNAPPY compress of n bytes at 64 KiB segments as ONE raw Snappy
+        stream in `joined` (uint8 tensor, or None: sizes only); offsets (int64 tensor, nseg + 1):
+        the exclusive prefix sum of the segments' body sizes; joined_len (int64 tensor, 1
+        entry, or None): the stream's length"""
+        cap = (joined.numel() if joined is not None else 0) if capacity is None else capacity
+        check(lib().bitar_hip_snappy_join(self.ctx, self._stream(stream), _ptr(slab), stride,
+                                          _ptr(sizes), n, seg, _ptr(offsets), _ptr(joined), cap,
+                                          _ptr(joined_len)))
+
+    def snappy_split(self, joined, length, n, starts, status, max_rounds=0, stats=None,
+                     stream=None):
+        """starts (int64 tensor, ceil(n / 65536) + 1): where each 64 KiB block of output begins
+        in the raw Snappy stream joined[:length] that declares n bytes, and `length` last;
+        status (int32 tensor, 1 entry): SNAPPY_SPLIT_*; stats (int32 tensor, 4 entries, or
+        None): rounds, tile walks, tiles, serial finish"""
+        check(lib().bitar_hip_snappy_split(self.ctx, self._stream(stream), _ptr(joined), length, n,
+                                           max_rounds, _ptr(starts), _ptr(status), _ptr(stats)))
+
+    def decompress_joined_into(self, joined, length, n, starts, out, produced, capacity=None,
+                               stream=None):
+        """every fragment of the stream between the starts of snappy_split, in one launch:
+        fragment k to out[k * 65536:], produced[k] its size or SEGMENT_ERROR"""
+        cap = out.numel() if capacity is None else capacity
+        check(lib().bitar_hip_snappy_decompress_joined(self.ctx, self._stream(stream),
+                                                       _ptr(joined), length, n, _ptr(starts),
+                                                       _ptr(out), cap, _ptr(produced)))
 
     def copy_batch(self, srcs, dsts, sizes, n, stream=None):
         """entry i: sizes[i] bytes from srcs[i] to dsts[i] (int64 / int32 device tensors)"""

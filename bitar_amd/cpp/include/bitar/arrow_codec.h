@@ -3,6 +3,7 @@
 // apps/demo_app.cc:148-150).
 //
 //   auto codec = bitar::MakeArrowCodec(arrow::Compression::ZSTD);    // or LZ4_FRAME, GZIP
+//   auto snappy = bitar::MakeArrowSnappyCodec();                     // Compression::SNAPPY
 //   auto opts = arrow::ipc::IpcWriteOptions::Defaults();
 //   opts.codec = std::shared_ptr<arrow::util::Codec>(std::move(*codec));
 //   // ... arrow::ipc::MakeStreamWriter(sink, schema, opts): bodies compressed on the GPU
@@ -21,6 +22,18 @@
 //              codec splits the stream again and inflates the segments in parallel (layout:
 //              src/gzip_frame.h).  Buffers above 21841 segments (about
 //              1.33 GiB: the index must fit the 16-bit XLEN) are NotImplemented.
+//   SNAPPY     (from MakeArrowSnappyCodec) ONE raw Snappy stream (no framing format; Parquet's default page codec): the
+//              varint of the length, then the elements of every segment's stream, joined on
+//              the device.  MaxCompressedLen is stock Snappy's 32 + n + n/6 (the stream is at
+//              most n + 4 per segment + 5; a smaller output buffer is taken when the stream
+//              fits, else CapacityError).  Decompress reads the varint, finds on the device
+//              where each 64 KiB block of output begins (a boundary scan: no index exists and
+//              none is needed) and decodes the blocks in one launch.  It takes every stream
+//              whose elements do not cross a multiple of 64 KiB of output and whose copies stay
+//              inside their block -- what stock writers produce.  Invalid: no preamble, a
+//              declared length above the output buffer, an element past the end, a wrong total;
+//              NotImplemented: "Snappy element across a 64 KiB block"; IOError: a block did not
+//              decode (corrupt, or a copy that reaches before its 64 KiB block).
 // Decompress walks the frame / block / member headers on the host (sizes only, no decoding)
 // and decodes every segment on the device.  Beyond what Compress writes it takes the streams
 // stock writers produce: Zstd frames of any content size up to 1 GiB (one segment each; a
@@ -32,7 +45,8 @@
 // on the device -- Zstd / LZ4 dictionaries, LZ4 blocks above 64 KiB, a stock gzip member above
 // 64 KiB (no index to decode it in parallel by) -- is NotImplemented, never a silent CPU
 // fallback.  Host and HBM buffers are both accepted (host data is staged through HBM).
-// Streaming compressors are NotImplemented.
+// Streaming compressors are NotImplemented.  The device context is opened by the first Compress
+// or Decompress: making a codec and asking for MaxCompressedLen need no device.
 #pragma once
 
 #include <arrow/result.h>
@@ -42,8 +56,13 @@
 
 namespace bitar {
 
-/// A Codec for arrow::Compression::ZSTD, LZ4_FRAME or GZIP on HIP device `device`.
+/// A Codec for arrow::Compression::ZSTD, LZ4_FRAME or GZIP on HIP device `device`.  SNAPPY has a
+/// factory of its own, below: here it is NotImplemented, as before that codec existed.
 arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowCodec(
     arrow::Compression::type type, int device = 0);
+
+/// A Codec for arrow::Compression::SNAPPY (one raw Snappy stream per buffer) on HIP device
+/// `device`.
+arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowSnappyCodec(int device = 0);
 
 }  // namespace bitar

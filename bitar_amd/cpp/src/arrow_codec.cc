@@ -1,8 +1,8 @@
-// arrow_codec.cc -- arrow::util::Codec adapters (ZSTD, LZ4_FRAME, GZIP) over the C ABI.
+// arrow_codec.cc -- arrow::util::Codec adapters (ZSTD, LZ4_FRAME, GZIP, SNAPPY) over the C ABI.
 // See include/bitar/arrow_codec.h for the stream layouts.  Every payload byte is compressed
 // and decompressed on the device; the host only walks frame / block / member headers (sizes)
 // and writes the 7-byte LZ4 frame header and EndMark, or the gzip member header and trailer
-// (gzip_frame.h).
+// (gzip_frame.h); of a Snappy stream it reads the preamble alone.
 #include "bitar/arrow_codec.h"
 
 #include <arrow/status.h>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bitar_hip.h"
+#include "bitar_hip_snappy.h"
 #include "gzip_frame.h"
 #include "hip_ctx.h"
 
@@ -75,9 +76,9 @@ struct Frame {
 
 class HipCodec : public arrow::util::Codec {
  public:
-  HipCodec(arrow::Compression::type type, int device, bitar_hip_ctx* ctx)
-      : type_(type), device_(device), ctx_(ctx) {}
+  HipCodec(arrow::Compression::type type, int device) : type_(type), device_(device) {}
   ~HipCodec() override {
+    if (!ctx_) return;
     for (void* p : {d_in_, d_slab_, d_sizes_, d_off_, d_frame_, d_out_, d_srcs_, d_aux_, d_join_,
                     d_meta_})
       if (p) bitar_hip_free(ctx_, p);
@@ -92,6 +93,8 @@ class HipCodec : public arrow::util::Codec {
 
   int64_t MaxCompressedLen(int64_t input_len, const uint8_t*) override {
     const uint64_t nseg = (static_cast<uint64_t>(input_len) + kSeg - 1) / kSeg;
+    if (type_ == arrow::Compression::SNAPPY)  // stock Snappy's bound (ours: n + 4 nseg + 5)
+      return 32 + input_len + input_len / 6;
     if (type_ == arrow::Compression::ZSTD)
       return static_cast<int64_t>(9 + nseg * bitar_hip_slot_size(BITAR_HIP_CODEC_ZSTD, kSeg));
     if (type_ == arrow::Compression::GZIP)  // header + index, the joined stream, trailer
@@ -114,6 +117,14 @@ class HipCodec : public arrow::util::Codec {
                                     int64_t output_buffer_len, uint8_t* output) override;
 
  private:
+  // The device context is opened by the first Compress or Decompress (under mu_), so a codec
+  // can be made, asked for its bounds and handed to a writer on a host that has no device.
+  arrow::Status Open() {
+    if (ctx_) return arrow::Status::OK();
+    bitar_hip_config cfg{1, 0};
+    BITAR_ABI(bitar_hip_open(device_, &cfg, &ctx_), "bitar_hip_open");
+    return arrow::Status::OK();
+  }
   // grow-only HBM scratch
   arrow::Status Reserve(void*& p, uint64_t& cap, uint64_t bytes) {
     if (bytes <= cap) return arrow::Status::OK();
@@ -146,6 +157,10 @@ class HipCodec : public arrow::util::Codec {
                                       uint8_t* output);
   arrow::Result<int64_t> DecompressGzip(uint64_t n, const uint8_t* input,
                                         int64_t output_buffer_len, uint8_t* output);
+  arrow::Result<int64_t> CompressSnappy(uint64_t n, const uint8_t* input,
+                                        int64_t output_buffer_len, uint8_t* output);
+  arrow::Result<int64_t> DecompressSnappy(uint64_t n, const uint8_t* input,
+                                          int64_t output_buffer_len, uint8_t* output);
   arrow::Status GzipIndexed(const gzf::Member& m, const uint8_t* input, uint8_t* output);
   arrow::Status GzipSingles(const std::vector<gzf::Member>& ms, size_t m0, size_t m1,
                             const uint8_t* d_in, uint8_t* output);
@@ -154,7 +169,7 @@ class HipCodec : public arrow::util::Codec {
 
   arrow::Compression::type type_;
   int device_;
-  bitar_hip_ctx* ctx_;
+  bitar_hip_ctx* ctx_ = nullptr;
   std::mutex mu_;  // one stream per codec; Arrow may share a codec between threads
   void *d_in_ = nullptr, *d_slab_ = nullptr, *d_sizes_ = nullptr, *d_off_ = nullptr,
        *d_frame_ = nullptr, *d_out_ = nullptr, *d_srcs_ = nullptr, *d_aux_ = nullptr,
@@ -167,10 +182,15 @@ arrow::Result<int64_t> HipCodec::Compress(int64_t input_len, const uint8_t* inpu
                                           int64_t output_buffer_len, uint8_t* output) {
   const std::lock_guard<std::mutex> lock(mu_);
   if (input_len < 0) return arrow::Status::Invalid("negative input length");
-  if (output_buffer_len < MaxCompressedLen(input_len, input))
+  // (SNAPPY takes any buffer its stream fits: CapacityError once the length is known)
+  if (type_ != arrow::Compression::SNAPPY && output_buffer_len < MaxCompressedLen(input_len, input))
     return arrow::Status::Invalid("output buffer smaller than MaxCompressedLen");
+  if (output_buffer_len < 0) return arrow::Status::Invalid("negative output buffer length");
+  ARROW_RETURN_NOT_OK(Open());
   const uint64_t n = static_cast<uint64_t>(input_len);
   if (type_ == arrow::Compression::GZIP) return CompressGzip(n, input, output_buffer_len, output);
+  if (type_ == arrow::Compression::SNAPPY)
+    return CompressSnappy(n, input, output_buffer_len, output);
   const uint64_t nseg = (n + kSeg - 1) / kSeg;
   const bool zstd = type_ == arrow::Compression::ZSTD;
   const bool out_dev = OnDevice(output);
@@ -337,9 +357,12 @@ arrow::Result<int64_t> HipCodec::Decompress(int64_t input_len, const uint8_t* in
                                             int64_t output_buffer_len, uint8_t* output) {
   const std::lock_guard<std::mutex> lock(mu_);
   if (input_len < 0 || output_buffer_len < 0) return arrow::Status::Invalid("negative length");
+  ARROW_RETURN_NOT_OK(Open());
   const uint64_t n = static_cast<uint64_t>(input_len);
   if (type_ == arrow::Compression::GZIP)
     return DecompressGzip(n, input, output_buffer_len, output);
+  if (type_ == arrow::Compression::SNAPPY)
+    return DecompressSnappy(n, input, output_buffer_len, output);
   const bool zstd = type_ == arrow::Compression::ZSTD;
   const bool in_dev = OnDevice(input);
   // the header walk needs the bytes on the host
@@ -835,10 +858,129 @@ arrow::Result<int64_t> HipCodec::DecompressGzip(uint64_t n, const uint8_t* input
   return static_cast<int64_t>(total);
 }
 
+// ---- SNAPPY (one raw stream per buffer) ----
+
+// The segments' raw streams joined on the device: varint(n), then every segment's elements.
+// Only the stream's length visits the host.
+arrow::Result<int64_t> HipCodec::CompressSnappy(uint64_t n, const uint8_t* input,
+                                                int64_t output_buffer_len, uint8_t* output) {
+  if (n > 0xFFFFFFFFull)
+    return arrow::Status::NotImplemented("Snappy buffers of 4 GiB and above (a 32-bit preamble)");
+  const uint64_t nseg = (n + kSeg - 1) / kSeg;
+  const uint64_t stride = bitar_hip_slot_size(BITAR_HIP_CODEC_SNAPPY, kSeg);
+  const uint64_t cap = n + 4 * nseg + 5;
+  const void* d_in = input;
+  if (n && !OnDevice(input)) {
+    ARROW_RETURN_NOT_OK(Reserve(d_in_, c_in_, n));
+    ARROW_RETURN_NOT_OK(Copy(d_in_, input, n));
+    d_in = d_in_;
+  }
+  ARROW_RETURN_NOT_OK(Reserve(d_slab_, c_slab_, nseg * stride));
+  ARROW_RETURN_NOT_OK(Reserve(d_sizes_, c_sizes_, nseg * 4));
+  ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, (nseg + 2) * 8));
+  ARROW_RETURN_NOT_OK(Reserve(d_join_, c_join_, cap));
+  auto* sizes = static_cast<uint32_t*>(d_sizes_);
+  auto* offs = static_cast<uint64_t*>(d_off_);
+  BITAR_ABI(bitar_hip_compress(ctx_, nullptr, BITAR_HIP_CODEC_SNAPPY, d_in, n, kSeg, d_slab_,
+                               stride, sizes),
+            "bitar_hip_compress");
+  BITAR_ABI(bitar_hip_snappy_join(ctx_, nullptr, d_slab_, stride, sizes, n, kSeg, offs, d_join_,
+                                  cap, offs + nseg + 1),
+            "bitar_hip_snappy_join");
+  uint64_t total = 0;
+  ARROW_RETURN_NOT_OK(Copy(&total, offs + nseg + 1, sizeof total));
+  ARROW_RETURN_NOT_OK(Sync());
+  if (total > static_cast<uint64_t>(output_buffer_len))
+    return arrow::Status::CapacityError("compressed stream exceeds the output buffer");
+  ARROW_RETURN_NOT_OK(Copy(output, d_join_, total));
+  ARROW_RETURN_NOT_OK(Sync());
+  return static_cast<int64_t>(total);
+}
+
+// Any raw Snappy stream whose elements do not cross a multiple of 64 KiB of output (every
+// stock writer's, and this codec's): the boundary scan finds the fragments on the device, one
+// launch decodes them.  The host reads the preamble, the scan's status and the produced sizes.
+arrow::Result<int64_t> HipCodec::DecompressSnappy(uint64_t n, const uint8_t* input,
+                                                  int64_t output_buffer_len, uint8_t* output) {
+  const bool in_dev = OnDevice(input);
+  uint8_t head[5] = {0, 0, 0, 0, 0};
+  const uint64_t nhead = std::min<uint64_t>(n, sizeof head);
+  if (in_dev) {
+    ARROW_RETURN_NOT_OK(Copy(head, input, nhead));
+    ARROW_RETURN_NOT_OK(Sync());
+  } else {
+    std::memcpy(head, input, nhead);
+  }
+  // the preamble, by the segment decoder's rule: <= 5 bytes, the fifth below 16, any padding
+  uint64_t declared = 0;
+  bool have = false;
+  for (uint64_t k = 0; k < nhead && !have; ++k) {
+    if (k == 4 && head[k] >= 16) break;
+    declared |= uint64_t(head[k] & 127u) << (7 * k);
+    have = head[k] < 128;
+  }
+  if (!have) return arrow::Status::Invalid("Snappy stream without a length preamble");
+  if (declared > static_cast<uint64_t>(output_buffer_len))
+    return arrow::Status::Invalid("declared Snappy length ", declared,
+                                  " exceeds the output buffer (", output_buffer_len, ")");
+  const uint64_t nfrag = (declared + kSeg - 1) / kSeg;
+  const uint8_t* d_in = input;
+  if (!in_dev) {
+    ARROW_RETURN_NOT_OK(Reserve(d_in_, c_in_, n + 16));
+    ARROW_RETURN_NOT_OK(Copy(d_in_, input, n));
+    d_in = static_cast<const uint8_t*>(d_in_);
+  }
+  const bool out_dev = OnDevice(output);
+  uint8_t* dout = output;
+  if (!out_dev) {
+    ARROW_RETURN_NOT_OK(Reserve(d_out_, c_out_, std::max<uint64_t>(declared, 16)));
+    dout = static_cast<uint8_t*>(d_out_);
+  }
+  ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, (nfrag + 1) * 8));
+  ARROW_RETURN_NOT_OK(Reserve(d_sizes_, c_sizes_, std::max<uint64_t>(nfrag * 4, 16)));
+  ARROW_RETURN_NOT_OK(Reserve(d_meta_, c_meta_, 16));
+  auto* starts = static_cast<uint64_t*>(d_off_);
+  auto* d_status = static_cast<uint32_t*>(d_meta_);
+  BITAR_ABI(bitar_hip_snappy_split(ctx_, nullptr, d_in, n, declared, 0, starts, d_status, nullptr),
+            "bitar_hip_snappy_split");
+  uint32_t status = 0;
+  ARROW_RETURN_NOT_OK(Copy(&status, d_status, sizeof status));
+  ARROW_RETURN_NOT_OK(Sync());
+  if (status == BITAR_HIP_SNAPPY_SPLIT_UNSUPPORTED)
+    return arrow::Status::NotImplemented("Snappy element across a 64 KiB block");
+  if (status != BITAR_HIP_SNAPPY_SPLIT_OK)
+    return arrow::Status::Invalid("corrupt Snappy stream: an element reads past its end, or its ",
+                                  "elements do not produce the declared ", declared, " bytes");
+  if (declared == 0) return 0;
+  auto* d_prod = static_cast<uint32_t*>(d_sizes_);
+  BITAR_ABI(bitar_hip_snappy_decompress_joined(ctx_, nullptr, d_in, n, declared, starts, dout,
+                                               declared, d_prod),
+            "bitar_hip_snappy_decompress_joined");
+  std::vector<uint32_t> prod(nfrag);
+  ARROW_RETURN_NOT_OK(Copy(prod.data(), d_prod, nfrag * 4));
+  const int rc = bitar_hip_sync(ctx_, nullptr);
+  if (rc != 0 && rc != BITAR_HIP_IO_ERROR) BITAR_ABI(rc, "segment codec");
+  uint64_t bad = nfrag;
+  for (uint64_t k = nfrag; k-- > 0;)
+    if (prod[k] != std::min<uint64_t>(kSeg, declared - k * kSeg)) bad = k;
+  if (rc != 0 || bad != nfrag)
+    return arrow::Status::IOError("Snappy block ", bad, " of ", nfrag, " did not decode: the ",
+                                  "stream is corrupt or has a copy that reaches before its ",
+                                  "64 KiB block");
+  if (!out_dev) {
+    ARROW_RETURN_NOT_OK(Copy(output, dout, declared));
+    ARROW_RETURN_NOT_OK(Sync());
+  }
+  return static_cast<int64_t>(declared);
+}
+
 }  // namespace
 
 arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowCodec(arrow::Compression::type type,
                                                                   int device) {
+  if (type == arrow::Compression::SNAPPY)
+    return arrow::Status::NotImplemented(
+        "HIP codec for snappy through MakeArrowCodec: use bitar::MakeArrowSnappyCodec");
   if (type != arrow::Compression::ZSTD && type != arrow::Compression::LZ4_FRAME &&
       type != arrow::Compression::GZIP)
     return arrow::Status::NotImplemented("HIP codec for ",
@@ -847,10 +989,11 @@ arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowCodec(arrow::Compres
   for (uint32_t seg : {1u, 13u, 59460u, 65536u})
     if (gzf::SlotSize(seg) != bitar_hip_slot_size(BITAR_HIP_CODEC_DEFLATE_DYNAMIC, seg))
       return arrow::Status::UnknownError("gzip_frame.h and the engine disagree on the slot size");
-  bitar_hip_config cfg{1, 0};
-  bitar_hip_ctx* ctx = nullptr;
-  BITAR_ABI(bitar_hip_open(device, &cfg, &ctx), "bitar_hip_open");
-  return std::unique_ptr<arrow::util::Codec>(new HipCodec(type, device, ctx));
+  return std::unique_ptr<arrow::util::Codec>(new HipCodec(type, device));
+}
+
+arrow::Result<std::unique_ptr<arrow::util::Codec>> MakeArrowSnappyCodec(int device) {
+  return std::unique_ptr<arrow::util::Codec>(new HipCodec(arrow::Compression::SNAPPY, device));
 }
 
 }  // namespace bitar

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bitar_hip.h"
+#include "../../include/bitar_hip_snappy.h"
 #define BITAR_COLUMN_DECLARATIONS_ONLY  // (the kernels are defined in the formats' files)
 #include "autopack.hip.h"
 #include "order.hip.h"
@@ -31,9 +32,26 @@ __global__ void lz4_decompress_kernel(const uint8_t* const*, const uint8_t*, uin
                                       uint32_t*, unsigned long long*, const uint32_t*);
 __global__ void snappy_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
                                        uint8_t* const*, uint32_t*, const uint32_t*);
+template <bool JOINED>
 __global__ void snappy_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
                                          const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
                                          uint32_t*, const uint32_t*);
+__global__ void snappy_joined_key_kernel(const uint64_t*, uint32_t, uint32_t*);
+__global__ void snappy_join_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint32_t*);
+__global__ void snappy_join_kernel(const uint8_t*, uint64_t, const uint32_t*, uint64_t*, uint32_t,
+                                   uint64_t, uint8_t*, uint64_t, uint64_t*, uint32_t*);
+__global__ void snappy_scan_init_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t*, uint32_t*,
+                                        uint4*, uint32_t*, uint32_t);
+__global__ void snappy_scan_walk_kernel(const uint8_t*, uint32_t, uint32_t, const uint32_t*, uint4*,
+                                        uint2*, const uint2*);
+__global__ void snappy_scan_resolve_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t, uint32_t,
+                                           uint32_t*, uint4*, const uint2*, uint4*, uint2*,
+                                           uint64_t*, uint32_t*);
+__global__ void snappy_scan_serial_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t, uint32_t,
+                                          uint32_t*, const uint4*, uint64_t*, uint32_t*, uint32_t);
+__global__ void snappy_scan_finish_kernel(const uint8_t*, uint32_t, uint64_t, uint32_t,
+                                          const uint32_t*, const uint4*, const uint4*, uint64_t*,
+                                          uint32_t*);
 __global__ void seg_cost_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
 __global__ void order_hist_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
                                   uint32_t*);
@@ -1142,7 +1160,7 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
     // coded size, largest first; stored segments (one literal: copies) last
     SegOrder ord;
     if (int r = ord.make(ctx, s, nseg, d_sizes, [](uint32_t*) {}, seg)) return r;
-    hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel, dim3(nseg), dim3(64), 0, s, srcs,
+    hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel<false>, dim3(nseg), dim3(64), 0, s, srcs,
                        slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
                        ord.order);
     if (int r = ord.release()) return r;
@@ -1462,6 +1480,133 @@ int bitar_hip_pack(bitar_hip_ctx* ctx, void* stream, const void* d_slab, uint64_
                        nseg, static_cast<uint8_t*>(d_frame));
     HIP_TRY(hipGetLastError(), "pack launch");
   }
+  return 0;
+}
+
+// ---- whole-buffer raw Snappy streams (snappy.hip) ----
+constexpr uint32_t kSnappyBlock = 65536;   // a stream decodes as fragments of this many bytes
+constexpr uint32_t kSnappyTile = 4096;     // bytes of the stream per tile walk (BITAR_SNAPPY_TILE)
+constexpr uint32_t kSnappyRounds = 64;     // default bound of scan rounds
+constexpr uint32_t kSnappyRoundGrid = 2048;  // workgroups of a round after the first
+// positions in the stream are 32-bit in the scan's records, and a tile's output count (its
+// literals, inside the stream, and <= 64 bytes per 2-byte copy) must fit 32 bits as well
+constexpr uint64_t kSnappyMaxStream = 0xFFF00000ull;
+
+int bitar_hip_snappy_join(bitar_hip_ctx* ctx, void* stream, const void* d_slab,
+                          uint64_t slot_stride, const uint32_t* d_sizes, uint64_t n, uint32_t seg,
+                          uint64_t* d_offsets, void* d_joined, uint64_t capacity,
+                          uint64_t* d_joined_len) {
+  if (int r = enter(ctx)) return r;
+  if (seg != kSnappyBlock)
+    return fail(BITAR_HIP_INVALID, "a joined Snappy stream is made of 65536-byte segments");
+  if (n > 0xFFFFFFFFull) return fail(BITAR_HIP_INVALID, "a Snappy preamble holds 32 bits");
+  const uint32_t nseg = (uint32_t)((n + kSnappyBlock - 1) / kSnappyBlock);
+  if (!d_offsets || (nseg && (!d_sizes || (d_joined && !d_slab))))
+    return fail(BITAR_HIP_INVALID, "null buffer");
+  if (nseg && d_joined && slot_stride < bitar_hip_slot_size(BITAR_HIP_CODEC_SNAPPY, seg))
+    return fail(BITAR_HIP_INVALID, "slot stride below the Snappy slot size");
+  hipStream_t s = pick_stream(ctx, stream);
+  void* body = nullptr;
+  HIP_TRY(hipMallocAsync(&body, 4ull * nseg + 16, s), "scratch allocation");
+  auto* d_body = static_cast<uint32_t*>(body);
+  if (nseg)
+    hipLaunchKernelGGL(bitar_hip::snappy_join_sizes_kernel, dim3((nseg + 255) / 256), dim3(256), 0,
+                       s, d_sizes, nseg, n, d_body);
+  hipLaunchKernelGGL(bitar_hip::scan_sizes_kernel, dim3(1), dim3(1024), 0, s, d_body, nseg,
+                     (uint64_t)kSnappyBlock + 6, d_offsets, err_word(ctx, s));
+  hipLaunchKernelGGL(bitar_hip::snappy_join_kernel, dim3(nseg + 1), dim3(64), 0, s,
+                     static_cast<const uint8_t*>(d_slab), slot_stride, d_body, d_offsets, nseg, n,
+                     static_cast<uint8_t*>(d_joined), capacity, d_joined_len, err_word(ctx, s));
+  const hipError_t le = hipGetLastError();
+  HIP_TRY(hipFreeAsync(body, s), "scratch release");
+  HIP_TRY(le, "join launch");
+  return 0;
+}
+
+int bitar_hip_snappy_split(bitar_hip_ctx* ctx, void* stream, const void* d_joined, uint64_t len,
+                           uint64_t n, uint32_t max_rounds, uint64_t* d_starts,
+                           uint32_t* d_status, uint32_t* d_stats) {
+  if (int r = enter(ctx)) return r;
+  if (!d_joined || !d_starts || !d_status) return fail(BITAR_HIP_INVALID, "null buffer");
+  if (len > kSnappyMaxStream)
+    return fail(BITAR_HIP_NOT_IMPLEMENTED, "Snappy streams above 4293918720 bytes");
+  if (n > 0xFFFFFFFFull) return fail(BITAR_HIP_INVALID, "a Snappy preamble holds 32 bits");
+  const uint64_t nfrag = (n + kSnappyBlock - 1) / kSnappyBlock;
+  const bool serial = !(max_rounds & BITAR_HIP_SNAPPY_NO_SERIAL_FINISH);
+  uint32_t rounds = max_rounds & ~BITAR_HIP_SNAPPY_NO_SERIAL_FINISH;
+  if (rounds == 0) rounds = kSnappyRounds;
+  if (rounds > 4096) return fail(BITAR_HIP_INVALID, "max_rounds above 4096");
+  const uint32_t ntile = len ? (uint32_t)((len + kSnappyTile - 1) / kSnappyTile) : 1u;
+  // an element gives at most 64 bytes for 3 of the stream's: more cannot be a stream's length
+  const uint32_t hopeless = n > 64 * len ? 1u : 0u;
+  hipStream_t s = pick_stream(ctx, stream);
+  const auto* src = static_cast<const uint8_t*>(d_joined);
+  const uint32_t len32 = (uint32_t)len;
+  // scratch: control words; per tile a record, a chain position, a dirty entry, round 1's result
+  void* scratch = nullptr;
+  HIP_TRY(hipMallocAsync(&scratch, 64 + 48ull * ntile, s), "scratch allocation");
+  auto* ctl = static_cast<uint32_t*>(scratch);
+  auto* rec = reinterpret_cast<uint4*>(static_cast<uint8_t*>(scratch) + 64);
+  uint4* cur = rec + ntile;
+  auto* list = reinterpret_cast<uint2*>(cur + ntile);
+  uint2* guess = list + ntile;
+  const uint64_t fill = (nfrag + 256) / 256;
+  hipLaunchKernelGGL(bitar_hip::snappy_scan_init_kernel, dim3((uint32_t)(fill < 1024 ? fill : 1024)),
+                     dim3(256), 0, s, src, len32, nfrag, d_starts, ctl, cur, d_status, hopeless);
+  for (uint32_t r = 0; r < rounds; ++r) {
+    const uint32_t grid = r == 0 || ntile < kSnappyRoundGrid ? ntile : kSnappyRoundGrid;
+    hipLaunchKernelGGL(bitar_hip::snappy_scan_walk_kernel, dim3(grid), dim3(64), 0, s, src, len32,
+                       ntile, ctl, rec, guess, r == 0 ? (const uint2*)nullptr : list);
+    hipLaunchKernelGGL(bitar_hip::snappy_scan_resolve_kernel, dim3(1), dim3(64), 0, s, src, len32,
+                       n, nfrag, ntile, ctl, rec, guess, cur, list, d_starts, d_status);
+  }
+  hipLaunchKernelGGL(bitar_hip::snappy_scan_serial_kernel, dim3(1), dim3(64), 0, s, src, len32, n,
+                     nfrag, ntile, ctl, cur, d_starts, d_status, serial ? 1u : 0u);
+  hipLaunchKernelGGL(bitar_hip::snappy_scan_finish_kernel, dim3(ntile), dim3(64), 0, s, src, len32,
+                     n, ntile, ctl, rec, cur, d_starts, d_status);
+  hipError_t le = hipGetLastError();
+  // rounds run, tile walks, tiles, 1 if the serial finish ran (the control words' order)
+  if (le == hipSuccess && d_stats) {
+    le = hipMemcpyAsync(d_stats, ctl + 3, 8, hipMemcpyDeviceToDevice, s);
+    if (le == hipSuccess) le = hipMemcpyAsync(d_stats + 3, ctl + 7, 4, hipMemcpyDeviceToDevice, s);
+    if (le == hipSuccess) le = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_stats + 2), (int)ntile, 1, s);
+  }
+  HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+  HIP_TRY(le, "scan launch");
+  return 0;
+}
+
+int bitar_hip_snappy_decompress_joined(bitar_hip_ctx* ctx, void* stream, const void* d_joined,
+                                       uint64_t len, uint64_t n, const uint64_t* d_starts,
+                                       void* d_out, uint64_t capacity, uint32_t* d_produced) {
+  if (int r = enter(ctx)) return r;
+  if (n == 0) return 0;
+  if (len > kSnappyMaxStream)
+    return fail(BITAR_HIP_NOT_IMPLEMENTED, "Snappy streams above 4293918720 bytes");
+  if (n > 0xFFFFFFFFull) return fail(BITAR_HIP_INVALID, "a Snappy preamble holds 32 bits");
+  if (capacity < n)
+    return fail(BITAR_HIP_CAPACITY_ERROR, "The decompressed_buffer is required to be >= " +
+                                              std::to_string(n) + " bytes");
+  if (!d_joined || !d_starts || !d_out || !d_produced) return fail(BITAR_HIP_INVALID, "null buffer");
+  const uint32_t nfrag = (uint32_t)((n + kSnappyBlock - 1) / kSnappyBlock);
+  hipStream_t s = pick_stream(ctx, stream);
+  // cost key: the fragment's coded size, as the slab decode's
+  SegOrder ord;
+  if (int r = ord.make(
+          ctx, s, nfrag, nullptr,
+          [&](uint32_t* keys) {
+            hipLaunchKernelGGL(bitar_hip::snappy_joined_key_kernel, dim3((nfrag + 255) / 256),
+                               dim3(256), 0, s, d_starts, nfrag, keys);
+          },
+          kSnappyBlock))
+    return r;
+  hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel<true>, dim3(nfrag), dim3(64), 0, s,
+                     reinterpret_cast<const uint8_t* const*>(d_starts),
+                     static_cast<const uint8_t*>(d_joined), n, (const uint32_t*)nullptr, nfrag,
+                     (uint32_t)len, static_cast<uint8_t*>(d_out), d_produced, err_word(ctx, s),
+                     ord.order);
+  if (int r = ord.release()) return r;
+  HIP_TRY(hipGetLastError(), "decompress launch");
   return 0;
 }
 

@@ -4,13 +4,17 @@
 //                             Snappy emitter; the stream is the LZ4 block's sequences re-emitted
 //                             as Snappy elements (tests/snappy_model.py), or the stored form
 //   snappy_decompress_kernel  any raw Snappy stream of <= 64 KiB (stock streams included), on
-//                             the decoders' stream window + history ring (stream_ring.hip.h)
+//                             the decoders' stream window + history ring (stream_ring.hip.h);
+//                             <true>: a fragment of a whole-buffer stream, without a preamble
+//   snappy_join_* / snappy_scan_*  one whole-buffer stream from the segments' streams, and the
+//                             boundary scan that finds its 64 KiB fragments again (further down)
 //
 // Format (include/bitar_hip.h, BITAR_HIP_CODEC_SNAPPY): the segment's length as a varint, then
 // elements -- a literal (tag (len-1) << 2, or 60 << 2 / 61 << 2 with 1 / 2 length bytes), a
 // copy-1 (2 bytes: 4 <= len <= 11, offset < 2048) or a copy-2 (3 bytes: len <= 64, 16-bit
 // offset).  A literal and the copy after it are separate elements, so a sequence costs two
 // chain steps in the decoder where LZ4 has one token.
+#include "order.hip.h"
 #include "stream_ring.hip.h"
 #include "window_parse.hip.h"
 
@@ -376,6 +380,11 @@ namespace snd {
 
 using namespace sr;
 
+// a whole-buffer stream decodes as fragments of kJoinBlock output bytes; a fragment's elements
+// take at most 5 stream bytes per output byte (a copy-4 of one byte)
+constexpr uint32_t kJoinBlock = 65536;
+constexpr uint64_t kJoinMaxFragment = 5ull * kJoinBlock;
+
 // stream bytes a batch may touch past ip: 64 candidate elements, the last a literal with a
 // length byte and 64 bytes, or a copy-4's five bytes
 constexpr uint32_t kBatchIn = 144;
@@ -409,6 +418,12 @@ __device__ __forceinline__ uint32_t walk_chain(uint32_t nx, uint64_t& chain) {
 
 }  // namespace snd
 
+// JOINED: fragment i of ONE whole-buffer stream (bitar_hip_snappy_decompress_joined, DESIGN.md
+// 4.23) instead of segment i of a slab.  The stream is at `slab`, its fragment starts (uint64,
+// nseg + 1 of them, as snappy_scan_* wrote them) at `srcs`, its declared length in `slot_stride`
+// and its size in bytes in `seg` (the block is kJoinBlock); `csizes` is not read.  A fragment
+// has no preamble: its length is the block, or what is left of the declared length.
+template <bool JOINED>
 __global__ __launch_bounds__(64) void snappy_decompress_kernel(
     const uint8_t* const* __restrict__ srcs, const uint8_t* __restrict__ slab,
     uint64_t slot_stride, const uint32_t* __restrict__ csizes, uint32_t nseg, uint32_t seg,
@@ -425,9 +440,23 @@ __global__ __launch_bounds__(64) void snappy_decompress_kernel(
   const uint32_t i = order ? order[blockIdx.x] : blockIdx.x;
 
   State s;
-  s.src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
-  s.csize = csizes[i];
-  s.dst = global_ptr(out + (uint64_t)i * seg);
+  bool ok = false;
+  uint32_t dlen = 0;
+  if constexpr (JOINED) {
+    // starts the scan did not write are all ones: such a fragment reads nothing and rejects
+    const uint64_t* starts = reinterpret_cast<const uint64_t*>(srcs);
+    const uint64_t s0 = starts[i], s1 = starts[i + 1];
+    ok = (s0 <= s1) & (s1 <= (uint64_t)seg) & (s1 - s0 <= kJoinMaxFragment);
+    const uint64_t left = slot_stride - (uint64_t)i * kJoinBlock;
+    dlen = left < kJoinBlock ? (uint32_t)left : kJoinBlock;
+    s.src = global_ptr(slab + (ok ? s0 : 0ull));
+    s.csize = ok ? (uint32_t)(s1 - s0) : 0u;
+    s.dst = global_ptr(out + (uint64_t)i * kJoinBlock);
+  } else {
+    s.src = global_ptr(srcs ? srcs[i] : slab + (uint64_t)i * slot_stride);
+    s.csize = csizes[i];
+    s.dst = global_ptr(out + (uint64_t)i * seg);
+  }
   s.cap = seg;
   s.ip = 0;
   s.op = 0;
@@ -442,16 +471,16 @@ __global__ __launch_bounds__(64) void snappy_decompress_kernel(
 
   // the preamble: a varint of <= 5 bytes whose fifth is below 16 (need not be minimal); a
   // declared length above the segment's capacity fails the segment
-  bool ok = false;
-  uint32_t dlen = 0;
-  for (uint32_t k = 0; k < 5 && s.ip < s.csize; ++k) {
-    const uint32_t c = byte_u(s, win, s.ip);
-    s.ip += 1;
-    if (k == 4 && c >= 16u) break;
-    dlen |= (c & 127u) << (7 * k);
-    if (c < 128u) { ok = true; break; }
+  if constexpr (!JOINED) {
+    for (uint32_t k = 0; k < 5 && s.ip < s.csize; ++k) {
+      const uint32_t c = byte_u(s, win, s.ip);
+      s.ip += 1;
+      if (k == 4 && c >= 16u) break;
+      dlen |= (c & 127u) << (7 * k);
+      if (c < 128u) { ok = true; break; }
+    }
+    if (dlen > seg) ok = false;
   }
-  if (dlen > seg) ok = false;
   s.cap = ok ? dlen : 0u;  // every store below is bounded by the declared length <= seg
 
   while (ok && s.ip < s.csize) {
@@ -601,6 +630,500 @@ __global__ __launch_bounds__(64) void snappy_decompress_kernel(
     produced[i] = 0xFFFFFFFFu;
     atomicOr(err, 1u);
   }
+}
+
+template __global__ void snappy_decompress_kernel<false>(const uint8_t* const*, const uint8_t*,
+                                                        uint64_t, const uint32_t*, uint32_t,
+                                                        uint32_t, uint8_t*, uint32_t*, uint32_t*,
+                                                        const uint32_t*);
+template __global__ void snappy_decompress_kernel<true>(const uint8_t* const*, const uint8_t*,
+                                                       uint64_t, const uint32_t*, uint32_t,
+                                                       uint32_t, uint8_t*, uint32_t*, uint32_t*,
+                                                       const uint32_t*);
+
+// the cost key of fragment i of a joined stream: the slab decode's key of its coded size
+// (util_kernels.hip order_key: the largest first, stored fragments last)
+__global__ __launch_bounds__(256) void snappy_joined_key_kernel(const uint64_t* __restrict__ starts,
+                                                                uint32_t nfrag,
+                                                                uint32_t* __restrict__ keys) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nfrag) return;
+  const uint64_t s0 = starts[i], s1 = starts[i + 1];
+  const uint64_t c = s1 >= s0 ? s1 - s0 : 0;
+  keys[i] = c >= snd::kJoinBlock
+                ? kOrderBins - 1u
+                : kOrderBins - 2u - (uint32_t)(c * (kOrderBins - 2u) / snd::kJoinBlock);
+}
+
+// ---- whole-buffer streams: the join and the boundary scan -------------------
+// snappy_join_sizes_kernel + scan_sizes_kernel + snappy_join_kernel write ONE raw stream from
+// the slots of a compress at 64 KiB segments: varint(n), then every segment's stream less its
+// own (minimal) preamble.  Stock readers decode it, and output position k * 65536 begins at an
+// element start in it.  The snappy_scan_* kernels find those starts in ANY raw stream (stock
+// writers cut at 64 KiB of input too) without a serial walk of the buffer:
+//   * the stream is cut into tiles of kTile bytes, a wave per tile.  A tile walk is the
+//     decoder's parse of "an element at position ip + lane" with walk_chain, without the output
+//     gather: from an entry e inside the tile it gives x, the first chain position at or past
+//     the tile's end (kInf when an element reads past the stream), and o, the output bytes of
+//     the elements that started in the tile;
+//   * round 1 walks every tile from a guess (tile 0 from the byte after the preamble, tile j
+//     from j * kTile); a wrong chain usually merges with the true one inside the tile;
+//   * the resolve (one wave) carries the true chain position c over the tiles' latest x; a
+//     tile whose entry is not c is dirty -- unless the first few elements from c leave the tile
+//     by themselves, whose end and output are then the tile's record (incompressible data: long
+//     literals from mid-tile to mid-tile) -- and the next round walks the dirty tiles only.
+//     Past a dirty tile the resolve goes on with the x of the tile's round-1 walk, not with
+//     the latest: a walk from a wrong entry that did not merge ends on a wrong chain, and in
+//     periodic data (columns) a wrong chain can hold for many tiles; the guesses start afresh
+//     at every tile;
+//   * at the fixpoint every active tile's (entry, x, o) is one walk's and entry[j + 1] == x[j]
+//     from the preamble on: the true chain.  Every round makes the first dirty tile final, and
+//     after the caller's bound of rounds one wave walks from the first unsettled tile to the end;
+//   * the finish: a tile whose output range holds a multiple of 65536 walks once more with
+//     the running count, writes starts[k] where an element starts at k * 65536 and reports an
+//     element that straddles one.
+// No workgroup waits for another: the order is the kernels' on the stream.  A record is written
+// whole by one wave (the tile's walk, or the resolve for a tile it settles itself).
+namespace sns {
+
+using snd::kJoinBlock;
+using snd::kNextStop;
+using snd::walk_chain;
+
+#ifndef BITAR_SNAPPY_TILE
+#define BITAR_SNAPPY_TILE 4096
+#endif
+constexpr uint32_t kTile = BITAR_SNAPPY_TILE;
+constexpr uint32_t kStage = kTile + 80;  // a walk parses 64 positions of up to 5 header bytes
+constexpr uint32_t kInf = 0xFFFFFFFFu;
+// The resolve follows the chain itself from a new entry for up to kFollow elements, as long as
+// they average kFollowBytes of the stream from the second on: where the chain is sparse -- long
+// literals with a copy between them, each landing mid-tile -- a tile walk from a wrong entry
+// rarely meets it, and every landing would cost a round.  Dense chains are the tile walks'.
+constexpr uint32_t kFollow = 16, kFollowBytes = 64;
+static_assert(kStage % 16 == 0 && kTile % 64 == 0, "tiles are staged in 16-byte blocks");
+
+// status values (include/bitar_hip.h): a worse one replaces a better one (atomicMax)
+constexpr uint32_t kOk = 0, kUnsupported = 1, kInvalid = 2, kIncomplete = 3;
+
+// control words of one scan
+enum : uint32_t { cNDirty, cFirst, cDone, cRounds, cWalks, cSettled, cP0, cSerial, cWords };
+
+struct El {
+  uint32_t next;  // position of the next element; kInf: this one reads past the stream
+  uint32_t out;   // its output bytes
+};
+
+// the element at pos from its tag and the four bytes behind it (whatever lies past the stream
+// is never used: an element whose header or literal leaves [0, len) is kInf)
+__device__ __forceinline__ El parse_el(uint32_t tag, uint32_t b1, uint32_t b2, uint32_t b3,
+                                       uint32_t b4, uint32_t pos, uint32_t len) {
+  const uint32_t kind = tag & 3u, code = tag >> 2;
+  const bool lit = kind == 0u;
+  const uint32_t nx = code < 60u ? 0u : code - 59u;  // a literal's length bytes
+  const uint32_t ext = b1 | (b2 << 8) | (b3 << 16) | (b4 << 24);
+  const uint32_t m = nx == 0u ? code : nx == 4u ? ext : ext & ((1u << (8u * nx)) - 1u);
+  const uint32_t hdr = lit ? 1u + nx : kind == 1u ? 2u : kind == 2u ? 3u : 5u;
+  const uint32_t rem = len - pos;
+  // bitwise: the compares stay vector compares
+  const bool bad = (pos >= len) | (hdr > rem) | (lit & (m >= rem - hdr));
+  El e;
+  e.next = bad ? kInf : pos + hdr + (lit ? m + 1u : 0u);
+  e.out = lit ? m + 1u : kind == 1u ? 4u + (code & 7u) : code + 1u;
+  return e;
+}
+
+// the element at the wave-uniform position pos, read from HBM (inside [0, len) only)
+__device__ __forceinline__ El parse_at(const GMEM uint8_t* src, uint32_t pos, uint32_t len) {
+  uint32_t b[5];
+#pragma unroll
+  for (uint32_t k = 0; k < 5; ++k) b[k] = (pos < len && k < len - pos) ? src[pos + k] : 0u;
+  return parse_el(b[0], b[1], b[2], b[3], b[4], pos, len);
+}
+
+// stream bytes [tb, tb + kStage) into buf, zeros past the stream's end
+__device__ __forceinline__ void stage_tile(uint8_t* buf, const GMEM uint8_t* src, uint32_t tb,
+                                           uint32_t len) {
+  lds_order();
+  for (uint32_t i = 16u * lane_id(); i < kStage; i += 16u * kWave) {
+    const uint64_t a = (uint64_t)tb + i;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (a + 16 <= len) {
+      __builtin_memcpy(&v, (const void*)(src + a), 16);
+    } else if (a < len) {
+      uint32_t w[4] = {0, 0, 0, 0};
+      for (uint32_t k = 0; k < (uint32_t)(len - a); ++k) w[k >> 2] |= (uint32_t)src[a + k] << (8u * (k & 3u));
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    *reinterpret_cast<uint4*>(buf + i) = v;
+  }
+  lds_order();
+}
+
+// The tile walk over a staged tile [tb, end): from e (tb <= e, e < end or nothing to do) to x
+// and o.  FIN: with the running output count `base` at e, the block starts among the elements
+// are written and a straddling element is reported.  At most kTile / 2 steps (an element is at
+// least 2 bytes); a step parses 64 positions and follows the chain through them.
+template <bool FIN>
+__device__ __forceinline__ void tile_walk(const uint8_t* buf, uint32_t tb, uint32_t end,
+                                          uint32_t len, uint32_t e, uint32_t& x, uint32_t& o,
+                                          uint64_t base, uint64_t n, uint64_t* __restrict__ starts,
+                                          bool& straddle) {
+  const uint32_t lane = lane_id();
+  uint32_t ip = e, sum = 0;
+  for (uint32_t it = 0; it < kTile && ip < end; ++it) {
+    const uint32_t r = ip - tb + lane;
+    const uint32_t pos = ip + lane;
+    const El el = parse_el(buf[r], buf[r + 1], buf[r + 2], buf[r + 3], buf[r + 4], pos, len);
+    const uint64_t E = ballot(el.next != kInf) & ballot(pos < end);
+    if (!(E & 1ull)) {  // (ip < end: the element at ip reads past the stream)
+      x = kInf;
+      o = sum;
+      return;
+    }
+    const uint32_t esz = el.next - pos;
+    const uint32_t nl = lane + (esz < kWave ? esz : kWave);  // < 128
+    const uint32_t inel = (uint32_t)(~E >> (nl & 63u)) & 1u;
+    uint64_t chain = 0;
+    walk_chain(nl | (inel * kNextStop), chain);
+    const bool in = (chain >> lane) & 1ull;
+    const uint32_t eo = in ? el.out : 0u;
+    const uint32_t incl = wave_incl_sum(eo);
+    if constexpr (FIN) {
+      const uint64_t a = base + sum + (incl - eo);
+      if (in & ((a & (kJoinBlock - 1u)) == 0u) & (a < n)) starts[a >> 16] = pos;
+      const uint64_t above = (a | (kJoinBlock - 1u)) + 1u;
+      if (ballot(in & (above < a + eo) & (above < n))) straddle = true;
+    }
+    sum += readlane(incl, kWave - 1);
+    ip = readlane(el.next, 63u - (uint32_t)__builtin_clzll(chain));
+  }
+  x = ip;
+  o = sum;
+}
+
+}  // namespace sns
+
+// body size of segment i: its stream less its minimal preamble; a failed segment
+// (BITAR_HIP_SEGMENT_ERROR) or a size no segment of this length can have stays as it is and
+// is clamped to 0 by the scan that follows (bit 2 of the error word)
+__global__ __launch_bounds__(256) void snappy_join_sizes_kernel(const uint32_t* __restrict__ sizes,
+                                                                uint32_t nseg, uint64_t n,
+                                                                uint32_t* __restrict__ body) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nseg) return;
+  const uint64_t left = n - (uint64_t)i * sns::kJoinBlock;
+  const uint32_t len = left < sns::kJoinBlock ? (uint32_t)left : sns::kJoinBlock;
+  const uint32_t nb = len < 128u ? 1u : len < 16384u ? 2u : 3u;
+  const uint32_t sz = sizes[i];
+  body[i] = (sz < nb || sz > len + 6u) ? 0xFFFFFFFFu : sz - nb;
+}
+
+// workgroup 0: varint(n) at the stream's head, its length at *joined_len; workgroup i + 1: the
+// body of segment i at pre + offsets[i] (offsets: the exclusive prefix sum of the body sizes).
+// A stream above `capacity` is not written at all (bit 1 of the error word).
+__global__ __launch_bounds__(64) void snappy_join_kernel(
+    const uint8_t* __restrict__ slab, uint64_t stride, const uint32_t* __restrict__ body,
+    uint64_t* __restrict__ offsets, uint32_t nseg, uint64_t n, uint8_t* __restrict__ joined,
+    uint64_t capacity, uint64_t* __restrict__ joined_len, uint32_t* __restrict__ err) {
+  const uint32_t lane = lane_id();
+  uint32_t pre = 1;
+  for (uint64_t v = n >> 7; v; v >>= 7) ++pre;  // <= 10 bytes
+  const uint64_t total = pre + offsets[nseg];
+  const bool fits = joined != nullptr && total <= capacity;
+  if (blockIdx.x == 0) {
+    if (lane == 0) {
+      if (joined_len != nullptr) *joined_len = total;
+      if (joined != nullptr && total > capacity) atomicOr(err, 2u);
+    }
+    if (fits && lane < pre)
+      joined[lane] = (uint8_t)(((n >> (7u * lane)) & 127u) | (lane + 1u < pre ? 128u : 0u));
+    return;
+  }
+  const uint32_t i = blockIdx.x - 1u;
+  if (i >= nseg || !fits) return;
+  const uint32_t b = body[i];
+  if (b == 0xFFFFFFFFu) return;  // (a failed segment joins as nothing)
+  const uint64_t left = n - (uint64_t)i * sns::kJoinBlock;
+  const uint32_t len = left < sns::kJoinBlock ? (uint32_t)left : sns::kJoinBlock;
+  const uint32_t nb = len < 128u ? 1u : len < 16384u ? 2u : 3u;
+  wave_copy_global(global_ptr(joined + pre + offsets[i]),
+                   global_ptr(slab + (uint64_t)i * stride + nb), b);
+}
+
+// starts[0, nfrag] = all ones (what no walk writes stays a reject for the fragment decoder);
+// thread 0 reads the preamble (<= 5 bytes, the fifth below 16, need not be minimal) and sets
+// the scan's control words.  status: kOk, or kInvalid without a preamble (then nothing else runs).
+__global__ __launch_bounds__(256) void snappy_scan_init_kernel(
+    const uint8_t* __restrict__ src, uint32_t len, uint64_t nfrag, uint64_t* __restrict__ starts,
+    uint32_t* __restrict__ ctl, uint4* __restrict__ cur, uint32_t* __restrict__ status,
+    uint32_t hopeless) {
+  for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k <= nfrag; k += 256ull * gridDim.x)
+    starts[k] = ~0ull;
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t p0 = 0;
+  bool ok = false;
+  for (uint32_t k = 0; k < 5 && k < len; ++k) {
+    const uint32_t c = src[k];
+    if (k == 4 && c >= 16u) break;
+    if (c < 128u) {
+      ok = true;
+      p0 = k + 1;
+      break;
+    }
+  }
+  ok = ok && !hopeless;
+  for (uint32_t k = 0; k < sns::cWords; ++k) ctl[k] = 0;
+  ctl[sns::cP0] = p0;
+  ctl[sns::cDone] = ok ? 0u : 1u;
+  cur[0] = make_uint4(p0, 0u, 0u, 0u);
+  *status = ok ? sns::kOk : sns::kInvalid;
+}
+
+// The walks of one round: round 1 (list == nullptr) every tile from its guess, later rounds
+// the tiles of the dirty list from their new entries.  A workgroup takes tiles blockIdx.x,
+// + gridDim.x, ...: at most ntile of them.
+__global__ __launch_bounds__(64) void snappy_scan_walk_kernel(
+    const uint8_t* __restrict__ src, uint32_t len, uint32_t ntile, const uint32_t* __restrict__ ctl,
+    uint4* __restrict__ rec, uint2* __restrict__ guess, const uint2* __restrict__ list) {
+  using namespace sns;
+  __shared__ __attribute__((aligned(16))) uint8_t buf[kStage];
+  if (ctl[cDone]) return;
+  const uint32_t count = list ? min(ctl[cNDirty], ntile) : ntile;
+  const uint32_t p0 = ctl[cP0];
+  const GMEM uint8_t* s = global_ptr(src);
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    uint32_t j = i, e = i == 0 ? p0 : i * kTile;
+    if (list) {
+      const uint2 d = list[i];
+      j = uniform(d.x);
+      e = uniform(d.y);
+    }
+    if (j >= ntile) continue;  // (the list is the resolve's: never taken)
+    const uint32_t tb = j * kTile;
+    const uint64_t te = (uint64_t)tb + kTile;
+    const uint32_t end = te < len ? (uint32_t)te : len;
+    stage_tile(buf, s, tb, len);
+    uint32_t x, o;
+    bool unused = false;
+    tile_walk<false>(buf, tb, end, len, e, x, o, 0, 0, nullptr, unused);
+    if (lane_id() == 0) {
+      rec[j] = make_uint4(e, x, o, 0u);
+      if (!list) guess[j] = make_uint2(x, o);  // round 1's result stays (the resolve's estimate)
+    }
+  }
+}
+
+// The resolve, one wave: from the first tile that is not final, 64 tiles per step.  The tiles
+// of a step whose entries already continue the chain (entry == the x before it) are taken in
+// one go, with a prefix sum of their o; the rest one by one, c and the output count in scalars.
+// For those the element at the likely c (the x before the tile) is parsed by the tile's lane
+// ahead of the scalar loop, so the loop waits for a load of its own only after a jump.
+__global__ __launch_bounds__(64) void snappy_scan_resolve_kernel(
+    const uint8_t* __restrict__ src, uint32_t len, uint64_t n, uint64_t nfrag, uint32_t ntile,
+    uint32_t* __restrict__ ctl, uint4* __restrict__ rec, const uint2* __restrict__ guess,
+    uint4* __restrict__ cur, uint2* __restrict__ list, uint64_t* __restrict__ starts,
+    uint32_t* __restrict__ status) {
+  using namespace sns;
+  if (ctl[cDone]) return;
+  const uint32_t lane = lane_id();
+  const GMEM uint8_t* s = global_ptr(src);
+  const uint32_t first = uniform(ctl[cFirst]);
+  const uint32_t walked = ctl[cRounds] ? ctl[cNDirty] : ntile;
+  const uint4 c0 = cur[first];
+  uint32_t c = uniform(c0.x);
+  uint64_t acc = uniform64((uint64_t)c0.z | ((uint64_t)c0.w << 32));
+  uint32_t ndirty = 0, newfirst = ntile;
+  for (uint32_t j0 = first; j0 < ntile; j0 += kWave) {
+    const uint32_t j = j0 + lane;
+    const bool live = j < ntile;
+    const uint32_t cnt = ntile - j0 < kWave ? ntile - j0 : kWave;
+    const uint4 r = live ? rec[j] : make_uint4(0, 0, 0, 0);
+    const uint2 g = live ? guess[j] : make_uint2(0, 0);
+    const uint32_t entry = r.x, x = r.y, o = r.z;
+    const uint64_t te = ((uint64_t)j + 1u) * kTile;
+    const uint32_t end = te < len ? (uint32_t)te : len;
+    const uint32_t before = wave_shr1(x);
+    const uint32_t prevx = lane == 0 ? c : before;
+    // the step's leading tiles that continue the chain as they are
+    const uint64_t cons = ballot(entry == prevx) & ballot(live);
+    const uint32_t K = ~cons ? (uint32_t)__builtin_ctzll(~cons) : kWave;
+    const uint32_t slo = wave_incl_sum(o & 0xFFFFu), shi = wave_incl_sum(o >> 16);
+    const uint64_t incl = (uint64_t)slo + ((uint64_t)shi << 16);
+    uint32_t curc = entry;
+    uint64_t curb = acc + incl - o;
+    if (K) {
+      c = readlane(x, K - 1);
+      acc += uniform64(((uint64_t)readlane(shi, K - 1) << 16) + readlane(slo, K - 1));
+    }
+    uint32_t nentry = 0, nx = 0, no = 0, dentry = 0;
+    bool isnew = false, isdirty = false;
+    if (K < cnt) {
+      // the others: the element at x of the tile before, if that lies in this tile
+      const bool want = live & (lane >= K) & (prevx < end) & (prevx >= j * kTile) & (prevx != entry);
+      El cand, cand2;
+      cand.next = cand2.next = kInf;
+      cand.out = cand2.out = 0;
+      if (want) {
+        cand = parse_at(s, prevx, len);
+        if (cand.next < end) cand2 = parse_at(s, cand.next, len);
+      }
+      const uint64_t parsed = ballot(want);
+      for (uint32_t l = K; l < cnt; ++l) {
+        uint32_t xl = readlane(x, l), ol = readlane(o, l);
+        const uint32_t el = readlane(entry, l), endl = readlane(end, l);
+        if (c >= endl) {
+          // a long literal jumps over the tile, and over every tile up to the one that holds c
+          const uint32_t to = c / kTile - j0;  // (c >= endl: past l; kInf: past every tile)
+          const uint32_t stop = max(l + 1u, to < cnt ? to : cnt);  // (c == len in the last tile)
+          const bool over = (lane >= l) & (lane < stop);
+          curc = over ? c : curc;
+          curb = over ? acc : curb;
+          l = stop - 1u;
+          continue;
+        }
+        const bool me = lane == l;
+        curc = me ? c : curc;
+        curb = me ? acc : curb;
+        {
+          if (el != c) {
+            // follow the chain from c while it is sparse (see kFollow); the first two elements
+            // are the lane's own parse where c is the x before the tile
+            const bool spec = readlane(prevx, l) == c && ((parsed >> l) & 1ull);
+            uint32_t q = c, osum = 0, nxt = 0;
+            bool left = false;
+            for (uint32_t k = 0; k < kFollow; ++k) {
+              El p;
+              if (spec && k < 2u) {
+                p.next = readlane(k ? cand2.next : cand.next, l);
+                p.out = readlane(k ? cand2.out : cand.out, l);
+              } else {
+                p = parse_at(s, q, len);
+                p.next = uniform(p.next);
+                p.out = uniform(p.out);
+              }
+              nxt = p.next;
+              if (p.next >= endl) {  // the chain leaves the tile (or an element is cut)
+                osum += p.next != kInf ? p.out : 0u;
+                left = true;
+                break;
+              }
+              osum += p.out;
+              q = p.next;
+              if (k >= 1u && q - c < kFollowBytes * (k + 1u)) break;
+            }
+            if (left) {
+              nentry = me ? c : nentry;
+              nx = me ? nxt : nx;
+              no = me ? osum : no;
+              isnew = isnew | me;
+              xl = nxt;
+              ol = osum;
+            } else {
+              // dirty: go on with the walk from the tile's guess, which no wrong entry made
+              dentry = me ? c : dentry;
+              isdirty = isdirty | me;
+              // (a guess that ran into a garbage literal "past the stream" is no estimate: the
+              // next tile's own guess entry is)
+              xl = readlane(g.x, l);
+              ol = readlane(g.y, l);
+              xl = (xl == kInf && endl < len) ? endl : xl;
+            }
+          }
+          c = xl;
+          acc += ol;
+        }
+      }
+    }
+    if (live) cur[j] = make_uint4(curc, 0u, (uint32_t)curb, (uint32_t)(curb >> 32));
+    if (isnew) rec[j] = make_uint4(nentry, nx, no, 0u);
+    const uint64_t dm = ballot(isdirty);
+    if (dm) {
+      const uint32_t at = ndirty + __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u));
+      if (isdirty) list[at] = make_uint2(j, dentry);
+      if (newfirst == ntile) newfirst = j0 + (uint32_t)__builtin_ctzll(dm);
+      ndirty += (uint32_t)__builtin_popcountll(dm);
+    }
+  }
+  if (lane != 0) return;
+  ctl[cRounds] += 1u;
+  ctl[cWalks] += walked;
+  ctl[cNDirty] = ndirty;
+  ctl[cFirst] = newfirst;
+  ctl[cSettled] = newfirst;  // (ntile when nothing is dirty)
+  if (ndirty == 0) {
+    ctl[cDone] = 1u;
+    if (c != len || acc != n) atomicMax(status, kInvalid);
+    else starts[nfrag] = len;
+  }
+}
+
+// After the last round: nothing to do when the resolve found no dirty tile.  Else one wave
+// walks from the first unsettled tile (its c and output count are final) to the stream's end
+// with the running count -- at most ntile tile walks -- or, where the caller forbade it, the
+// status is kIncomplete.
+__global__ __launch_bounds__(64) void snappy_scan_serial_kernel(
+    const uint8_t* __restrict__ src, uint32_t len, uint64_t n, uint64_t nfrag, uint32_t ntile,
+    uint32_t* __restrict__ ctl, const uint4* __restrict__ cur, uint64_t* __restrict__ starts,
+    uint32_t* __restrict__ status, uint32_t allowed) {
+  using namespace sns;
+  __shared__ __attribute__((aligned(16))) uint8_t buf[kStage];
+  if (ctl[cDone]) return;
+  const uint32_t lane = lane_id();
+  if (!allowed) {
+    if (lane == 0) atomicMax(status, kIncomplete);
+    return;
+  }
+  const GMEM uint8_t* s = global_ptr(src);
+  const uint32_t f = uniform(ctl[cSettled]);
+  const uint4 c0 = cur[f < ntile ? f : 0u];
+  uint32_t c = uniform(c0.x);
+  uint64_t acc = uniform64((uint64_t)c0.z | ((uint64_t)c0.w << 32));
+  bool straddle = false;
+  for (uint32_t it = 0; it < ntile && c < len; ++it) {
+    const uint32_t tb = c / kTile * kTile;
+    const uint64_t te = (uint64_t)tb + kTile;
+    const uint32_t end = te < len ? (uint32_t)te : len;
+    stage_tile(buf, s, tb, len);
+    uint32_t x, o;
+    tile_walk<true>(buf, tb, end, len, c, x, o, acc, n, starts, straddle);
+    c = x;
+    acc += o;
+  }
+  if (lane != 0) return;
+  ctl[cSerial] = 1u;
+  if (c != len || acc != n) atomicMax(status, kInvalid);
+  else starts[nfrag] = len;
+  if (straddle) atomicMax(status, kUnsupported);
+}
+
+// The finish, a wave per settled tile: an active tile whose output range [base, base + o)
+// holds a multiple of 65536 walks once more with the running count.
+__global__ __launch_bounds__(64) void snappy_scan_finish_kernel(
+    const uint8_t* __restrict__ src, uint32_t len, uint64_t n, uint32_t ntile,
+    const uint32_t* __restrict__ ctl, const uint4* __restrict__ rec, const uint4* __restrict__ cur,
+    uint64_t* __restrict__ starts, uint32_t* __restrict__ status) {
+  using namespace sns;
+  __shared__ __attribute__((aligned(16))) uint8_t buf[kStage];
+  const uint32_t j = blockIdx.x;
+  if (j >= ntile || j >= ctl[cSettled]) return;
+  const uint4 cu = cur[j];
+  const uint4 r = rec[j];
+  const uint32_t tb = j * kTile;
+  const uint64_t te = (uint64_t)tb + kTile;
+  const uint32_t end = te < len ? (uint32_t)te : len;
+  const uint32_t c = uniform(cu.x);
+  const uint64_t base = uniform64((uint64_t)cu.z | ((uint64_t)cu.w << 32));
+  const uint32_t o = uniform(r.z);
+  if (c >= end || c != uniform(r.x)) return;  // jumped over (a settled tile's entry is its c)
+  const uint64_t border = (base + (kJoinBlock - 1u)) & ~(uint64_t)(kJoinBlock - 1u);
+  if (border >= base + o || border >= n) return;
+  stage_tile(buf, global_ptr(src), tb, len);
+  uint32_t x, o2;
+  bool straddle = false;
+  tile_walk<true>(buf, tb, end, len, c, x, o2, base, n, starts, straddle);
+  if (straddle && lane_id() == 0) atomicMax(status, kUnsupported);
 }
 
 }  // namespace bitar_hip

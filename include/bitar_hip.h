@@ -555,6 +555,9 @@ int bitar_hip_deflate_split(bitar_hip_ctx* ctx, void* stream, const void* d_join
 int bitar_hip_crc32_combine(bitar_hip_ctx* ctx, void* stream, const uint64_t* d_sums, uint64_t n,
                             uint32_t seg, uint32_t nseg, uint32_t* d_crc);
 
+/* Whole-buffer raw Snappy streams (one stream per buffer, joined from SNAPPY segments and
+ * split again on the device) have their entry points in bitar_hip_snappy.h. */
+
 /* Decoder selection of one context.  The decoders are interchangeable (every one accepts and
  * rejects exactly what the oracle does); the options pick which kernels run, for tests and
  * tuning.  No reference counterpart: the BlueField engine has one decoder. */
