@@ -27,12 +27,14 @@ CODEC_SNAPPY = 6  # one raw Snappy stream per segment (the LZ4 parse; decodes st
 #   RUNPACK   per-segment run lengths
 #   AUTOPACK  per segment the smallest of the applicable four above (no format of its own: any id
 #             decodes all of them)
+#   CASCADE   RUNPACK's runs, their values and lengths packed by INTPACK (no candidate of AUTOPACK)
 COLUMN_CODECS = {
     "INTPACK": (8, 4, (1, 2, 4, 8)),
     "FLTPACK": (16, 5, (4, 8)),
     "DICTPACK": (24, 6, (4, 8, 16)),
     "RUNPACK": (32, 7, (1, 2, 4, 8, 16)),
     "AUTOPACK": (40, None, (1, 2, 4, 8, 16)),
+    "CASCADE": (64, 8, (1, 2, 4, 8)),
 }
 _COLUMN_IDS = {name: {w: base + w.bit_length() - 1 for w in widths}
                for name, (base, _, widths) in COLUMN_CODECS.items()}
@@ -207,6 +209,11 @@ def codec_runpack(width):
 def codec_autopack(width):
     """the AUTOPACK codec id of an element width of 1, 2, 4, 8 or 16 bytes"""
     return _column_codec("AUTOPACK", width)
+
+
+def codec_cascade(width):
+    """the CASCADE codec id of an element width of 1, 2, 4 or 8 bytes"""
+    return _column_codec("CASCADE", width)
 
 
 def max_distance(codec):
@@ -440,7 +447,8 @@ class Engine:
         empty streams and tags of no format}.  Reads the tag bytes only (a strided view of the
         slab on torch's current stream); waits for them."""
         t = self.torch
-        formats = {nibble: name for name, (_, nibble, _) in COLUMN_CODECS.items() if nibble}
+        formats = {nibble: name for name, (_, nibble, _) in COLUMN_CODECS.items()
+                   if nibble and nibble <= 7}  # (AUTOPACK's four)
         if nseg == 0:
             return {k: 0 for k in (*formats.values(), "stored", "other")}
         tags = t.as_strided(slab, (nseg,), (stride,)).to(t.int64)

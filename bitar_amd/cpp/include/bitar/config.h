@@ -59,12 +59,15 @@ using Class_HIP_GFX950 =
 /// streams RUNPACK, INTPACK, DICTPACK and FLTPACK give at element_width() (1, 2, 4, 8 or 16; a
 /// codec is tried at the widths it has), and decodes each segment by its tag -- for columns whose
 /// shape is not known in advance or changes along the column.
+/// CASCADE is the engine's cascaded run-length codec (likewise its own): RUNPACK's
+/// runs with their values and lengths bit-packed by INTPACK -- sorted keys, coarse timestamps,
+/// clustered status codes, flag bytes; element_width() is 1, 2, 4 or 8.  No candidate of AUTOPACK.
 /// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
 /// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
 /// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
-  AUTOPACK = 8, SNAPPY = 9
+  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
@@ -126,7 +129,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK and AUTOPACK have no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }
@@ -201,7 +204,7 @@ class HipConfiguration : public Configuration<Class_HIP_GFX950> {
   }
   /// The element width alone: what Codec::INTPACK (1, 2, 4 or 8 bytes), Codec::FLTPACK (4 or
   /// 8 bytes), Codec::DICTPACK (4, 8 or 16 bytes), Codec::RUNPACK and Codec::AUTOPACK (1, 2, 4,
-  /// 8 or 16 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it.
+  /// 8 or 16 bytes) and Codec::CASCADE (1, 2, 4 or 8 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it.
   void set_element_width(std::uint8_t element_width) { element_width_ = element_width; }
 
   static HipConfiguration Defaults() { return {}; }

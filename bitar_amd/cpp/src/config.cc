@@ -16,6 +16,7 @@ std::string_view ToString(Codec c) {
     case Codec::RUNPACK: return "RUNPACK";
     case Codec::AUTOPACK: return "AUTOPACK";
     case Codec::SNAPPY: return "SNAPPY";
+    case Codec::CASCADE: return "CASCADE";
   }
   return "UNKNOWN";
 }

@@ -1,6 +1,7 @@
-// bitpack.hip.h -- what the bit-packing codecs share (intpack.hip, fltpack.hip; gfx950, wave64):
-// wave reductions over DPP, element loads and stores at any alignment, and the payload emitter
-// that writes a miniblock's bit string as aligned dwords.
+// bitpack.hip.h -- what the bit-packing codecs share (intpack.hip, fltpack.hip, cascade.hip;
+// gfx950, wave64): wave reductions over DPP, element loads and stores at any alignment, the
+// payload emitter that writes a miniblock's bit string as aligned dwords, and INTPACK's plan and
+// miniblock decode over elements from anywhere (intpack.hip, cascade.hip).
 //
 // Payload of a miniblock of 64 elements at width b: 8 * b bytes, element t at bits
 // [t*b, (t+1)*b) of the little-endian bit string.  Lane t holds element t.
@@ -229,6 +230,179 @@ __device__ __forceinline__ typename Elem<W>::U extract_field(const GMEM uint8_t*
     if (b < 32) r &= (1u << b) - 1;
   }
   return r;
+}
+
+// ---- INTPACK's plan and its miniblock decode, over elements from anywhere ---------------------
+// (intpack.hip takes them from the segment in global memory and puts them back there;
+// cascade.hip plans the runs its head scan leaves in LDS and decodes into LDS.)
+// A source of elements is a callable: src(idx) is element idx < m; kKeepShift: see load_values.
+
+template <uint32_t W>
+struct GlobalElems {
+  static constexpr bool kKeepShift = false;
+  const GMEM uint8_t* p;
+  __device__ __forceinline__ typename Elem<W>::U operator()(uint32_t idx) const {
+    return load_elem<W>(p + (uint64_t)idx * W);
+  }
+};
+
+// the x of this lane's element idx: the element (mode 0) or its difference to the one before
+// (mode 1), mod 2^(8W); lanes at or past m get 0
+template <uint32_t W, class SRC>
+__device__ __forceinline__ void load_values(const SRC& src, uint32_t idx, uint32_t m,
+                                            typename Elem<W>::U& plain, typename Elem<W>::U& delta) {
+  using U = typename Elem<W>::U;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  const uint32_t lane = lane_id();
+  U v = 0;
+  if (idx < m) v = src(idx);
+  U prev = dpp<0x138, 0xf>(v, (U)0);  // wave_shr:1
+  // (A source may ask for the shifted value to stay a move of its own.  Folded into the
+  // subtraction as v_subrev_u32_dpp, which the compiler does where element idx - 1 never needs a
+  // second load, the first miniblock's differences came out negated on gfx950: cascade.hip's
+  // single-read path.  INTPACK's kernels never get that form, and the barrier costs them time.)
+  if constexpr (SRC::kKeepShift) __asm__ volatile("" : "+v"(prev));
+  if (lane == 0 && idx > 0 && idx < m) prev = src(idx - 1);
+  U d = (v - prev) & mask;
+  if (idx < kMini) {  // the first miniblock: x_0 = x_1, or 0 when there is no element 1
+    const U d1 = (U)__shfl(d, 1);
+    if (idx == 0) d = m > 1 ? d1 : 0;
+  }
+  plain = v;
+  delta = idx < m ? d : 0;
+}
+
+template <uint32_t W>
+__device__ __forceinline__ typename Elem<W>::S as_signed(typename Elem<W>::U x) {
+  using S = typename Elem<W>::S;
+  constexpr uint32_t sh = 8 * sizeof(S) - 8 * W;
+  return (S)(x << sh) >> sh;
+}
+
+// Block `blk` (miniblocks 4 blk .. 4 blk + 3) of m elements in both modes: this lane's x, the
+// block's reference and the miniblocks' widths (0 for a miniblock past the last)
+template <uint32_t W>
+struct BlockPlan {
+  typename Elem<W>::U x[2][4], ref[2];
+  uint32_t b[2][4];
+  // this lane's residual in miniblock 4 blk + j (0 at or past m)
+  __device__ __forceinline__ typename Elem<W>::U residual(uint32_t md, uint32_t j, bool in) const {
+    using U = typename Elem<W>::U;
+    constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+    return in ? (U)((x[md][j] - ref[md]) & mask) : (U)0;
+  }
+};
+template <uint32_t W, class SRC>
+__device__ __forceinline__ void plan_block(const SRC& src, uint32_t blk, uint32_t m,
+                                           BlockPlan<W>& p) {
+  using U = typename Elem<W>::U;
+  using S = typename Elem<W>::S;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  const uint32_t lane = lane_id();
+  S lo[2] = {(S)(~(U)0 >> 1), (S)(~(U)0 >> 1)};
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint32_t idx = (blk * 4 + j) * kMini + lane;
+    load_values<W>(src, idx, m, p.x[0][j], p.x[1][j]);
+    if (idx < m) {
+      lo[0] = imin(lo[0], as_signed<W>(p.x[0][j]));
+      lo[1] = imin(lo[1], as_signed<W>(p.x[1][j]));
+    }
+  }
+#pragma unroll
+  for (uint32_t md = 0; md < 2; ++md) {
+    p.ref[md] = (U)wave_min<S, U>(lo[md]) & mask;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const uint32_t idx = (blk * 4 + j) * kMini + lane;
+      p.b[md][j] = bit_length(wave_or<U>(p.residual(md, j, idx < m)));
+    }
+  }
+}
+
+// Where the parts of a stream of L bytes at width W lie
+template <uint32_t W>
+struct Layout {
+  uint32_t m, tail, nmb, nblk, wid_at, ref_at, pay_at;
+  static constexpr uint32_t base_at = 4;
+  __device__ __forceinline__ Layout(uint32_t L, uint32_t mode) {
+    m = L / W;
+    tail = L - m * W;
+    nmb = (m + kMini - 1) / kMini;
+    nblk = (nmb + 3) / 4;
+    wid_at = 4 + (mode == 1 ? W : 0);
+    ref_at = wid_at + nmb;
+    pay_at = ref_at + nblk * W;
+  }
+};
+
+// mode: delta only when strictly smaller, stored (mode 2, size 4 + L) when nothing is gained;
+// sum[md] = the payload bytes of mode md
+template <uint32_t W>
+__device__ __forceinline__ uint32_t choose_mode(uint32_t L, const uint32_t (&sum)[2], uint32_t& size) {
+  const Layout<W> lay(L, 0);
+  const uint32_t fixed = lay.pay_at + lay.tail;
+  const uint32_t size0 = fixed + sum[0], size1 = fixed + W + sum[1];
+  const uint32_t mode = size1 < size0 ? 1u : 0u;
+  size = mode ? size1 : size0;
+  if (size < 4u + L) return mode;
+  size = 4u + L;
+  return 2u;
+}
+
+// the first dword of a stream
+template <uint32_t W>
+__device__ __forceinline__ uint32_t stream_head(uint32_t mode, uint32_t L) {
+  constexpr uint32_t kLog = W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : 3;
+  return 0x40u | mode << 2 | kLog | (L - 1) << 16;
+}
+// what a decoder accepts of bytes 0 and 1 (the width bits apart)
+__device__ __forceinline__ bool valid_head(uint32_t tag, uint32_t rsv) {
+  return (tag >> 4) == 4u && ((tag >> 2) & 3u) != 3u && rsv == 0;
+}
+
+// The widths of a packed stream of csize bytes (mode 0 or 1): false for a stream that must be
+// rejected -- too short for its header arrays, a width above 8 W, a size other than what the
+// widths add up to.  sink(k, b, off) gets this lane's miniblock k < nmb, its width and the byte
+// offset of its payload; `run` becomes the payload's size.
+template <uint32_t W, class SINK>
+__device__ __forceinline__ bool scan_widths(const GMEM uint8_t* src, uint32_t csize,
+                                            const Layout<W>& lay, uint32_t& run, SINK&& sink) {
+  const uint32_t lane = lane_id();
+  if (csize < lay.pay_at + lay.tail) return false;  // (so the header arrays lie inside the stream)
+  run = 0;
+  bool bad = false;
+  for (uint32_t k0 = 0; k0 < lay.nmb; k0 += kWave) {
+    const uint32_t k = k0 + lane;
+    const uint32_t b = k < lay.nmb ? src[lay.wid_at + k] : 0u;
+    bad = bad || b > 8 * W;
+    const uint32_t incl = wave_incl_sum(8u * b);
+    if (k < lay.nmb) sink(k, b, run + incl - 8u * b);
+    run += readlane(incl, 63);
+  }
+  if (ballot(bad) != 0) return false;  // (each width <= 64: run <= 64 KiB * 8, no overflow)
+  return lay.pay_at + run + lay.tail == csize;
+}
+
+// this lane's element of miniblock k of width b whose payload starts at mb; `carry` is the last
+// element so far (mode 1)
+template <uint32_t W>
+__device__ __forceinline__ typename Elem<W>::U unpack_miniblock(
+    const GMEM uint8_t* src, const Layout<W>& lay, uint32_t mode, uint32_t k, uint32_t b,
+    const GMEM uint8_t* mb, typename Elem<W>::U& carry) {
+  using U = typename Elem<W>::U;
+  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
+  const uint32_t idx = k * kMini + lane_id();
+  U r = 0;
+  if (b) r = extract_field<W>(mb, b);
+  const U ref = load_elem<W>(src + lay.ref_at + (k / 4) * W);
+  U v = (r + ref) & mask;
+  if (mode) {
+    if (idx == 0) v = load_elem<W>(src + lay.base_at);
+    v = wave_incl_add<U>(v) + carry;
+    carry = lane63(v);
+  }
+  return v;
 }
 
 }  // namespace ipk

@@ -27,34 +27,6 @@ namespace bitar_hip {
 
 namespace ipk {
 
-// the x of this lane's element idx: the element (mode 0) or its difference to the one before
-// (mode 1), mod 2^(8W); lanes at or past m get 0
-template <uint32_t W>
-__device__ __forceinline__ void load_values(const GMEM uint8_t* src, uint32_t idx, uint32_t m,
-                                            typename Elem<W>::U& plain, typename Elem<W>::U& delta) {
-  using U = typename Elem<W>::U;
-  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
-  const uint32_t lane = lane_id();
-  U v = 0;
-  if (idx < m) v = load_elem<W>(src + (uint64_t)idx * W);
-  U prev = dpp<0x138, 0xf>(v, (U)0);  // wave_shr:1
-  if (lane == 0 && idx > 0 && idx < m) prev = load_elem<W>(src + (uint64_t)(idx - 1) * W);
-  U d = (v - prev) & mask;
-  if (idx < kMini) {  // the first miniblock: x_0 = x_1, or 0 when there is no element 1
-    const U d1 = (U)__shfl(d, 1);
-    if (idx == 0) d = m > 1 ? d1 : 0;
-  }
-  plain = v;
-  delta = idx < m ? d : 0;
-}
-
-template <uint32_t W>
-__device__ __forceinline__ typename Elem<W>::S as_signed(typename Elem<W>::U x) {
-  using S = typename Elem<W>::S;
-  constexpr uint32_t sh = 8 * sizeof(S) - 8 * W;
-  return (S)(x << sh) >> sh;
-}
-
 struct Shared {
   uint8_t wid[2][kMaxMini];                                // widths of mode 0 / mode 1
   __attribute__((aligned(8))) uint8_t ref[2][kMaxBlk * 8]; // references, W bytes each
@@ -69,40 +41,26 @@ __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32
                                                  GMEM uint8_t* dst, uint32_t* size_out,
                                                  Shared& sh) {
   using U = typename Elem<W>::U;
-  using S = typename Elem<W>::S;
   constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
-  constexpr uint32_t kLog = W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : 3;
   const uint32_t lane = lane_id();
-  const uint32_t m = L / W, tail = L - m * W;
-  const uint32_t nmb = (m + kMini - 1) / kMini, nblk = (nmb + 3) / 4;
+  const Layout<W> lay(L, 0);
+  const uint32_t m = lay.m, tail = lay.tail, nmb = lay.nmb, nblk = lay.nblk;
+  const GlobalElems<W> elems{src};
 
-  // ---- plan: both modes' references and widths in one sweep -------------------------------
+  // ---- plan: both modes' references and widths in one sweep (bitpack.hip.h) -----------------
   uint32_t sum[2] = {0, 0};
   for (uint32_t blk = 0; blk < nblk; ++blk) {
-    U x[2][4];
-    S lo[2] = {(S)(~(U)0 >> 1), (S)(~(U)0 >> 1)};
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t idx = (blk * 4 + j) * kMini + lane;
-      load_values<W>(src, idx, m, x[0][j], x[1][j]);
-      if (idx < m) {
-        lo[0] = imin(lo[0], as_signed<W>(x[0][j]));
-        lo[1] = imin(lo[1], as_signed<W>(x[1][j]));
-      }
-    }
+    BlockPlan<W> p;
+    plan_block<W>(elems, blk, m, p);
 #pragma unroll
     for (uint32_t md = 0; md < 2; ++md) {
-      const U ref = (U)wave_min<S, U>(lo[md]) & mask;
-      if (lane == 0) set_lds_ref<W>(sh.ref[md], blk, ref);
+      if (lane == 0) set_lds_ref<W>(sh.ref[md], blk, p.ref[md]);
 #pragma unroll
       for (uint32_t j = 0; j < 4; ++j) {
         const uint32_t k = blk * 4 + j;
-        const uint32_t idx = k * kMini + lane;
-        const U r = idx < m ? (U)((x[md][j] - ref) & mask) : (U)0;
-        const uint32_t b = bit_length(wave_or<U>(r));
         if (k < nmb) {
-          if (lane == 0) sh.wid[md][k] = (uint8_t)b;
-          sum[md] += 8u * b;
+          if (lane == 0) sh.wid[md][k] = (uint8_t)p.b[md][j];
+          sum[md] += 8u * p.b[md][j];
         }
       }
     }
@@ -110,21 +68,19 @@ __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32
   lds_order();
 
   // ---- mode: delta only when strictly smaller, stored when nothing is gained ---------------
-  const uint32_t fixed = 4u + nmb + nblk * W + tail;
-  const uint32_t size0 = fixed + sum[0], size1 = fixed + W + sum[1];
-  const uint32_t mode = size1 < size0 ? 1u : 0u;
-  const uint32_t total = mode ? size1 : size0;
+  uint32_t total;
+  const uint32_t mode = choose_mode<W>(L, sum, total);
   GMEM uint32_t* head = reinterpret_cast<GMEM uint32_t*>(dst);  // (slots are 16-B aligned)
-  if (!(total < 4u + L)) {
+  if (mode == 2) {
     if (lane == 0) {
-      if constexpr (STORE) *head = 0x40u | 2u << 2 | kLog | (L - 1) << 16;
-      *size_out = 4u + L;
+      if constexpr (STORE) *head = stream_head<W>(2, L);
+      *size_out = total;
     }
     if constexpr (STORE) wave_copy_global(dst + 4, src, L);
     return;
   }
   if (lane == 0) {
-    *head = 0x40u | mode << 2 | kLog | (L - 1) << 16;
+    *head = stream_head<W>(mode, L);
     *size_out = total;
   }
   uint32_t pos = 4;
@@ -145,7 +101,7 @@ __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32
     if (b == 0) continue;
     const uint32_t idx = k * kMini + lane;
     U xs[2];
-    load_values<W>(src, idx, m, xs[0], xs[1]);
+    load_values<W>(elems, idx, m, xs[0], xs[1]);
     const U ref = lds_ref<W>(sh.ref[mode], k / 4);
     const U r = idx < m ? (U)(((mode ? xs[1] : xs[0]) - ref) & mask) : (U)0;
     emit.put(r, b);
@@ -166,46 +122,24 @@ __device__ __forceinline__ bool decompress_packed(const GMEM uint8_t* src, uint3
                                                   uint32_t L, uint32_t mode, GMEM uint8_t* dst,
                                                   DecShared& sh) {
   using U = typename Elem<W>::U;
-  constexpr U mask = (U)(~(U)0 >> (8 * sizeof(U) - 8 * W));
   const uint32_t lane = lane_id();
-  const uint32_t m = L / W, tail = L - m * W;
-  const uint32_t nmb = (m + kMini - 1) / kMini, nblk = (nmb + 3) / 4;
-  const uint32_t base_at = 4, wid_at = 4 + (mode ? W : 0), ref_at = wid_at + nmb;
-  const uint32_t pay_at = ref_at + nblk * W;
-  if (csize < pay_at + tail) return false;  // (so the header arrays lie inside the stream)
+  const Layout<W> lay(L, mode);
+  const uint32_t m = lay.m, tail = lay.tail, nmb = lay.nmb;
 
   // widths -> offsets; the stream's size must be exactly what they add up to
-  uint32_t run = 0;
-  bool bad = false;
-  for (uint32_t k0 = 0; k0 < nmb; k0 += kWave) {
-    const uint32_t k = k0 + lane;
-    const uint32_t b = k < nmb ? src[wid_at + k] : 0u;
-    bad = bad || b > 8 * W;
-    const uint32_t incl = wave_incl_sum(8u * b);
-    if (k < nmb) {
-      sh.wid[k] = (uint8_t)b;
-      sh.off[k] = run + incl - 8u * b;
-    }
-    run += readlane(incl, 63);
-  }
-  if (ballot(bad) != 0) return false;  // (each width <= 64: run <= 64 KiB * 8, no overflow)
-  if (pay_at + run + tail != csize) return false;
+  uint32_t run;
+  if (!scan_widths<W>(src, csize, lay, run, [&](uint32_t k, uint32_t b, uint32_t off) {
+        sh.wid[k] = (uint8_t)b;
+        sh.off[k] = off;
+      }))
+    return false;
   lds_order();
 
-  const GMEM uint8_t* pay = src + pay_at;
+  const GMEM uint8_t* pay = src + lay.pay_at;
   U carry = 0;
   for (uint32_t k = 0; k < nmb; ++k) {
-    const uint32_t b = sh.wid[k];
     const uint32_t idx = k * kMini + lane;
-    U r = 0;
-    if (b) r = extract_field<W>(pay + sh.off[k], b);
-    const U ref = load_elem<W>(src + ref_at + (k / 4) * W);
-    U v = (r + ref) & mask;
-    if (mode) {
-      if (idx == 0) v = load_elem<W>(src + base_at);
-      v = wave_incl_add<U>(v) + carry;
-      carry = lane63(v);
-    }
+    const U v = unpack_miniblock<W>(src, lay, mode, k, sh.wid[k], pay + sh.off[k], carry);
     if (idx < m) store_elem<W>(dst + (uint64_t)idx * W, v);
   }
   if (lane < tail) dst[m * W + lane] = pay[run + lane];
@@ -228,7 +162,7 @@ struct IntPack {
                                                        uint32_t seg, GMEM uint8_t* dst,
                                                        DecShared& sh) {
     const uint32_t mode = (tag >> 2) & 3u;
-    bool ok = (tag >> 4) == kNibble && mode != 3u && rsv == 0 && L <= seg;
+    bool ok = ipk::valid_head(tag, rsv) && L <= seg;
     if (ok && mode == 2) {
       ok = decode_stored(src, csize, L, dst);
     } else if (ok) {

@@ -381,7 +381,9 @@ extern "C++" {
 //   Listed-decoder order (AUTOPACK decompress): list f belongs to family f of this table, tag
 //     nibble 4 + f -- INTPACK, FLTPACK, DICTPACK, RUNPACK -- which is what autopack_route_kernel
 //     writes.
-enum ColumnFamily : int { kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kColumnFamilies };
+enum ColumnFamily : int {
+  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kColumnFamilies
+};
 struct ColumnRow {
   uint32_t base, nibble, widths;
 };
@@ -391,6 +393,7 @@ constexpr ColumnRow kColumn[kColumnFamilies] = {
     {BITAR_HIP_CODEC_DICTPACK32 - 2, 6, 4 | 8 | 16},         // DICTPACK
     {BITAR_HIP_CODEC_RUNPACK8, 7, 1 | 2 | 4 | 8 | 16},       // RUNPACK
     {BITAR_HIP_CODEC_AUTOPACK8, 0, 1 | 2 | 4 | 8 | 16},      // AUTOPACK
+    {BITAR_HIP_CODEC_CASCADE8, 8, 1 | 2 | 4 | 8},            // CASCADE (no candidate of AUTOPACK)
 };
 constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
 constexpr uint32_t kListedDecoders = 4;
@@ -439,6 +442,7 @@ static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
     case kFltPack: return width_kernel<bitar_hip::FltPack, kFltPack, STORE>(lg);
     case kDictPack: return width_kernel<bitar_hip::DictPack, kDictPack, STORE>(lg);
     case kRunPack: return width_kernel<bitar_hip::RunPack, kRunPack, true>(lg);
+    case kCascade: return width_kernel<bitar_hip::Cascade, kCascade, true>(lg);
     default: return nullptr;
   }
 }
@@ -448,6 +452,7 @@ static DecompressKernel decompress_kernel(uint32_t f) {
     case kIntPack: return bitar_hip::column_decompress_kernel<bitar_hip::IntPack, LISTED>;
     case kFltPack: return bitar_hip::column_decompress_kernel<bitar_hip::FltPack, LISTED>;
     case kDictPack: return bitar_hip::column_decompress_kernel<bitar_hip::DictPack, LISTED>;
+    case kCascade: return bitar_hip::column_decompress_kernel<bitar_hip::Cascade, LISTED>;
     default: return bitar_hip::column_decompress_kernel<bitar_hip::RunPack, LISTED>;
   }
 }
@@ -660,7 +665,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   const ColumnCodec cc = column_codec(codec);
   if (cc && cc.family != kAutoPack) {
     // one streaming kernel, the same work for every segment: plain order (intpack.hip,
-    // fltpack.hip, dictpack.hip, runpack.hip)
+    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip)
     hipLaunchKernelGGL(compress_kernel<true>(cc.family, cc.lg), dim3((uint32_t)nseg), dim3(64), 0,
                        s, in, n, seg, slab, slot_stride, dsts, d_sizes);
   }

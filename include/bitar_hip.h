@@ -216,7 +216,42 @@ enum bitar_hip_codec {
   BITAR_HIP_CODEC_AUTOPACK16 = 41,
   BITAR_HIP_CODEC_AUTOPACK32 = 42,
   BITAR_HIP_CODEC_AUTOPACK64 = 43,
-  BITAR_HIP_CODEC_AUTOPACK128 = 44
+  BITAR_HIP_CODEC_AUTOPACK128 = 44,
+  /* CASCADE: RUNPACK's runs with their values and lengths packed by INTPACK --
+   * the "RLE, delta, bit-pack" cascade -- for columns whose runs are themselves regular: sorted
+   * keys, coarse timestamps, clustered status codes, flag bytes.  The id is 64 + log2(w) for
+   * w = 1, 2, 4 or 8 bytes; no reference counterpart and no stock library reads the format.  It
+   * is no candidate of AUTOPACK.  One stream per segment of L bytes, m = L / w elements compared
+   * as byte patterns, the last L - m*w bytes are the tail:
+   *   byte 0      0x80 | mode << 3 | log2(w)    mode 0 cascade, 1 stored
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                           size = 4 + L
+   *   cascade:    LE16(r - 1)      r = number of runs, 1 <= r <= min(m, 32768)
+   *               LE16(vsize - 1)
+   *               values           an INTPACK stream (tag 0x4_, any of its three modes) of width w
+   *                                whose "segment" is the r*w bytes of the runs' values; vsize bytes
+   *               lengths          an INTPACK stream of width 2 whose "segment" is the 2r bytes
+   *                                LE16(run length - 1) of the runs
+   *               tail
+   *   size = 8 + vsize + lsize + (L - m*w)
+   * The encoder's runs are maximal, the two sub-streams are byte for byte what INTPACK writes
+   * for those bytes (its choice between plain, delta and stored and its 4-byte header
+   * included), and the cascade form is taken when r <= 32768 and its size is strictly below
+   * 4 + L; every other segment is stored (m = 0 and a tie included).  The decoder takes w from
+   * the tag (all four ids select it) and rejects, before it writes anything: a high nibble
+   * other than 8, log2(w) above 3, byte 1 != 0, L > seg, a stored form whose size is not 4 + L,
+   * a cascade form shorter than 8 bytes, r > min(m, 32768), a vsize that leaves no room for a
+   * 4-byte lengths header and the tail, a values sub-stream that INTPACK's own rules reject or
+   * whose tag width is not w or whose L field is not r*w, the same for the lengths sub-stream
+   * with width 2 and 2r (its size must be exactly the rest of the stream less the tail), run
+   * lengths that do not add up to exactly m.  A rejected segment's output range is left
+   * untouched.  Streams no encoder writes decode: equal neighbouring values, a sub-stream in a
+   * mode that is not its smallest, a cascade form larger than 4 + L. */
+  BITAR_HIP_CODEC_CASCADE8 = 64,
+  BITAR_HIP_CODEC_CASCADE16 = 65,
+  BITAR_HIP_CODEC_CASCADE32 = 66,
+  BITAR_HIP_CODEC_CASCADE64 = 67
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -244,6 +279,11 @@ enum bitar_hip_codec {
   ((width) == 1 ? BITAR_HIP_CODEC_AUTOPACK8 : (width) == 2 ? BITAR_HIP_CODEC_AUTOPACK16 : \
    (width) == 4 ? BITAR_HIP_CODEC_AUTOPACK32 : (width) == 8 ? BITAR_HIP_CODEC_AUTOPACK64 : \
    BITAR_HIP_CODEC_AUTOPACK128)
+
+/* The CASCADE id of an element width of 1, 2, 4 or 8 bytes. */
+#define BITAR_HIP_CODEC_CASCADE(width) \
+  ((width) == 1 ? BITAR_HIP_CODEC_CASCADE8 : (width) == 2 ? BITAR_HIP_CODEC_CASCADE16 : \
+   (width) == 4 ? BITAR_HIP_CODEC_CASCADE32 : BITAR_HIP_CODEC_CASCADE64)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -296,14 +336,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK and AUTOPACK, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK and AUTOPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
