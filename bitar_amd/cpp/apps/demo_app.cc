@@ -1,6 +1,6 @@
 // demo_app.cc -- the bitar demo/benchmark harness on MI355X (reference apps/demo_app.cc).
 //
-//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy]
+//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy|rans]
 //            [--seg N] [--devices N] [--workers N] [--ipc-codec none|zstd|lz4]
 //            [--filter shuffle|bitshuffle --element-width 2|4|8|16]
 //   demo_app --synthetic N ...      (no file: N bytes of a generated mixed buffer)
@@ -316,6 +316,7 @@ int main(int argc, char** argv) {
   const auto codec = codec_name == "lz4"    ? bitar::Codec::LZ4
                      : codec_name == "zstd" ? bitar::Codec::ZSTD
                      : codec_name == "snappy" ? bitar::Codec::SNAPPY
+                     : codec_name == "rans" ? bitar::Codec::RANS
                                             : bitar::Codec::DEFLATE;
   // a per-segment transposition of --element-width byte values in front of the codec
   if (filter_name != "none" && filter_name != "shuffle" && filter_name != "bitshuffle") {

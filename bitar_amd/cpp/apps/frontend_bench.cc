@@ -2,7 +2,7 @@
 // reference user measures with demo_app's EvaluateSync (reference apps/demo_app.cc:332-357,
 // PrintPerfNumbers 82-89), as one JSON line for bench.py.
 //
-//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy]
+//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy|rans]
 //                  [--steps K] [--warmup W] [--no-host]
 //
 // Leg "frontend": an HBM-resident arrow::Buffer of N bytes (the synthetic input of kind K,
@@ -136,6 +136,7 @@ int main(int argc, char** argv) {
   auto cfg = std::make_unique<bitar::HipConfiguration>(bitar::HipConfiguration::Defaults());
   cfg->set_codec(codec == "zstd" ? bitar::Codec::ZSTD
                  : codec == "snappy" ? bitar::Codec::SNAPPY
+                 : codec == "rans" ? bitar::Codec::RANS
                  : codec == "deflate" ? bitar::Codec::DEFLATE : bitar::Codec::LZ4);
   cfg->set_decompressed_seg_size32(seg);
   // the slot pool holds a whole call's outputs from the start (no critical-path growth)

@@ -62,12 +62,16 @@ using Class_HIP_GFX950 =
 /// CASCADE is the engine's cascaded run-length codec (likewise its own): RUNPACK's
 /// runs with their values and lengths bit-packed by INTPACK -- sorted keys, coarse timestamps,
 /// clustered status codes, flag bytes; element_width() is 1, 2, 4 or 8.  No candidate of AUTOPACK.
+/// RANS is the engine's order-0 rANS entropy coder (likewise its own): 64
+/// interleaved states per segment, for bytes whose gain is their histogram and not their repeats
+/// -- non-decimal floats behind Filter::SHUFFLE or BITSHUFFLE, embeddings, noisy sensor words;
+/// one level, no window, no chained operations; filters and checksums as for LZ4.
 /// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
 /// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
 /// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
-  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10
+  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
@@ -129,7 +133,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE have no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }

@@ -17,6 +17,7 @@ std::string_view ToString(Codec c) {
     case Codec::AUTOPACK: return "AUTOPACK";
     case Codec::SNAPPY: return "SNAPPY";
     case Codec::CASCADE: return "CASCADE";
+    case Codec::RANS: return "RANS";
   }
   return "UNKNOWN";
 }

@@ -339,6 +339,7 @@ std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     case Codec::SNAPPY: return BITAR_HIP_CODEC_SNAPPY;
+    case Codec::RANS: return BITAR_HIP_CODEC_RANS;
     default:
       return c.huffman_enc() == HuffmanEncoding::FIXED ? BITAR_HIP_CODEC_DEFLATE
                                                       : BITAR_HIP_CODEC_DEFLATE_DYNAMIC;
@@ -804,6 +805,7 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
     return arrow::Status::Invalid("Burst size must be greater than 0");
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
       configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::SNAPPY &&
+      configuration_->codec() != Codec::RANS &&
       !internal::IsColumnCodec(configuration_->codec()))
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
@@ -830,6 +832,10 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
       return arrow::Status::Invalid(column->name, " cannot be combined with chained operations "
                                     "(max_sgl_segs > 1)");
   }
+  // (the same holds for RANS: one stream is one segment's 64 states)
+  if (configuration_->codec() == Codec::RANS && configuration_->max_sgl_segs() > 1)
+    return arrow::Status::Invalid("RANS cannot be combined with chained operations "
+                                  "(max_sgl_segs > 1)");
   // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
   // other value is refused rather than ignored (the reference always sets 1)
   if (configuration_->level() < 1 || configuration_->level() > 9)
@@ -849,8 +855,8 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   while ((1u << window) < reach) ++window;
   encoder_window_ = window;
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
-  // (a column codec has no matches and no window: ignored, reported 0)
-  if (internal::IsColumnCodec(configuration_->codec())) {
+  // (a column codec and RANS have no matches and no window: ignored, reported 0)
+  if (internal::IsColumnCodec(configuration_->codec()) || configuration_->codec() == Codec::RANS) {
     encoder_window_ = 0;
     configuration_->set_window_size(0);
   } else if (configuration_->window_size() == 0) {

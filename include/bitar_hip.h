@@ -251,7 +251,44 @@ enum bitar_hip_codec {
   BITAR_HIP_CODEC_CASCADE8 = 64,
   BITAR_HIP_CODEC_CASCADE16 = 65,
   BITAR_HIP_CODEC_CASCADE32 = 66,
-  BITAR_HIP_CODEC_CASCADE64 = 67
+  BITAR_HIP_CODEC_CASCADE64 = 67,
+  /* RANS: an order-0 rANS entropy coder with 64 interleaved states for byte
+   * segments whose gain is their histogram and not their repeats -- non-decimal floats behind the
+   * shuffle filter, embeddings and weights, noisy sensor words, residuals.  No reference
+   * counterpart and no stock library reads the format (tests/rans_model.py is a numpy reader and
+   * writer).  Ids 68..71 are left for a fifth CASCADE width.  One stream per segment of L bytes:
+   *   byte 0      0xA0 | mode                mode 0 rans, 1 stored
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                           size = 4 + L
+   *   rans:       bitmap   32 bytes, bit s (byte s >> 3, bit s & 7) set iff byte value s occurs
+   *               freqs    for the k-th present symbol in ascending order, f - 1 in bits
+   *                        [12k, 12k + 12) of a little-endian bit string, zero-padded to an even
+   *                        number of bytes
+   *               words    nw little-endian 16-bit words, in the order the encoder emitted them
+   *               states   64 x LE32, the encoder's final state of lane 0..63
+   *   size = 36 + tsize + 2*nw + 256,  tsize = 2 * ceil(12 * nsym / 16)
+   * Frequencies: with c[s] the count of s and nsym the number of present symbols,
+   * f[s] = 1 + floor(c[s] * (4096 - nsym) / L), and the deficit 4096 - sum(f) goes to the most
+   * frequent symbol (the lowest value on a tie); cum[s] is the sum of f[t] over t < s.
+   * Coder: symbol i belongs to lane i mod 64 and step i div 64; 32-bit states start at 2^16.  The
+   * encoder runs the steps from the last to the first; an active lane with state x and symbol s
+   * emits x & 0xFFFF and shifts x right by 16 when x >= f[s] * 2^20, then
+   * x = (x div f[s]) * 4096 + x mod f[s] + cum[s]; a step's words are appended in ascending lane
+   * order, and after step 0 the 64 states are written.  The decoder runs the steps forward with
+   * p = nw: slot = x & 4095, s the symbol whose [cum, cum + f) holds slot,
+   * x = f[s] * (x >> 12) + slot - cum[s]; the n lanes with x < 2^16, ranked r in lane order, then
+   * take x = x << 16 | words[p - n + r], and p -= n.
+   * The rans form is taken iff its size is strictly below 4 + L.  The decoder rejects: a high
+   * nibble other than 0xA, a mode above 1, byte 1 != 0, L > seg, a stored form whose size is not
+   * 4 + L, a rans form shorter than 36 + 2 + 256 bytes, an empty bitmap, frequencies that do not
+   * sum to 4096, non-zero pad bits in freqs, a size for which 2*nw is negative or odd, an initial
+   * state below 2^16 -- all before the first output byte -- and a refill that needs more words
+   * than remain, words left over at the end, or a final state other than 2^16 (rANS's own
+   * integrity check) after part of the segment's output range may have been written.  Nothing
+   * outside that range is written.  Streams no encoder writes decode: any table that sums to
+   * 4096, a rans form larger than 4 + L. */
+  BITAR_HIP_CODEC_RANS = 72
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -336,14 +373,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK and CASCADE have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
