@@ -120,6 +120,7 @@ def lib():
         "bitar_hip_decompress_slab": (i32, [vp, vp, u32, vp, u64, vp, u32, u32, vp, u64, vp]),
         "bitar_hip_sync": (i32, [vp, vp]),
         "bitar_hip_pack": (i32, [vp, vp, vp, u64, vp, u32, vp, vp]),
+        "bitar_hip_pack_lz4f": (i32, [vp, vp, vp, u64, u32, vp, u64, vp, vp, vp, vp]),
         "bitar_hip_fill": (i32, [vp, vp, i32, u64, vp, u64]),
         "bitar_hip_fill_at": (i32, [vp, vp, i32, u64, u64, vp, u64]),
         "bitar_hip_checksum": (i32, [vp, vp, u32, vp, u64, u32, vp, u32, vp]),
@@ -342,6 +343,16 @@ class Engine:
     def pack(self, slab, stride, sizes, nseg, offsets, frame=None, stream=None):
         check(lib().bitar_hip_pack(self.ctx, self._stream(stream), _ptr(slab), stride,
                                    _ptr(sizes), nseg, _ptr(offsets), _ptr(frame)))
+
+    def pack_lz4f(self, data, n, seg, slab, stride, sizes, framed, offsets, frame=None,
+                  stream=None):
+        """the data blocks of an LZ4 frame from the slots of a CODEC_LZ4 compress of n bytes at
+        segment size seg: framed (int32 tensor, nseg) the blocks' sizes with their size fields,
+        offsets (int64 tensor, nseg + 1) their exclusive prefix sum, frame (uint8 tensor, or
+        None: sizes only, data and slab are not read)"""
+        check(lib().bitar_hip_pack_lz4f(self.ctx, self._stream(stream), _ptr(data), n, seg,
+                                        _ptr(slab), stride, _ptr(sizes), _ptr(framed),
+                                        _ptr(offsets), _ptr(frame)))
 
     def fill(self, kind, seed, out, n=None, stream=None, offset=0):
         """bytes [offset, offset + n) of the synthetic stream `kind` into `out`."""

@@ -3,7 +3,8 @@
 // Modes: `cpu` (no GPU needed: configuration rules, discovery errors), `gpu <in> <outdir>`
 // (Compress/Decompress/Recycle/async through real devices; compressed segments are written
 // to <outdir> so the Python side can check them with zlib / liblz4), `arrow <in> <outdir>`
-// (the util::Codec adapters) and `pool <0|1> <in>` (the pools' debug poisoning, expected on
+// (the util::Codec adapters), `arrow_large <in> <outdir>` (the ZSTD and LZ4_FRAME adapters on
+// one input of more than 1024 segments, nothing else) and `pool <0|1> <in>` (the pools' debug poisoning, expected on
 // or off, and buffers the front-end did not allocate: hipHostRegister'd host memory and HBM
 // owned by another context).  Built twice: against the release libbitar.so (-DNDEBUG) and
 // the debug variant (lib/debug/libbitar.so).  Mirrors the reference's
@@ -613,6 +614,42 @@ void ArrowCodecTests(const std::string& input_path, const std::string& outdir) {
   }
 }
 
+// The ZSTD and LZ4_FRAME adapters on an input of more than 1024 segments of 64 KiB (an Arrow
+// IPC body above 64 MiB): the frame index behind Compress is a prefix sum that walks the sizes
+// 1024 at a time, and the adapter sizes its copy by that index's last entry.  Compress, then
+// the GPU decode and the stock decode of the stream, each compared with the input.
+void ArrowLargeTests(const std::string& input_path) {
+  const auto data = ReadFile(input_path);
+  const size_t n = data.size();
+  CHECK(n > size_t{1024} * 65536);
+  for (auto type : {arrow::Compression::ZSTD, arrow::Compression::LZ4_FRAME}) {
+    auto codec = bitar::MakeArrowCodec(type, 0);
+    CHECK_OK(codec.status());
+    if (!codec.ok()) continue;
+    auto& c = *codec;
+    const int64_t max = c->MaxCompressedLen(static_cast<int64_t>(n), data.data());
+    std::vector<uint8_t> comp(static_cast<size_t>(max));
+    auto clen = c->Compress(static_cast<int64_t>(n), data.data(), max, comp.data());
+    CHECK_OK(clen.status());
+    if (!clen.ok()) continue;
+    CHECK(*clen > 0 && *clen <= max);
+    std::vector<uint8_t> back(n + 1);
+    auto dlen = c->Decompress(*clen, comp.data(), static_cast<int64_t>(n), back.data());
+    CHECK_OK(dlen.status());
+    CHECK(dlen.ok() && *dlen == static_cast<int64_t>(n) &&
+          std::memcmp(back.data(), data.data(), n) == 0);
+    auto stock = arrow::util::Codec::Create(type);
+    CHECK_OK(stock.status());
+    if (!stock.ok()) continue;
+    std::vector<uint8_t> sb(n + 1);
+    auto r = (*stock)->Decompress(*clen, comp.data(), static_cast<int64_t>(n), sb.data());
+    CHECK_OK(r.status());
+    CHECK(r.ok() && *r == static_cast<int64_t>(n) && std::memcmp(sb.data(), data.data(), n) == 0);
+    std::cout << (type == arrow::Compression::ZSTD ? "zstd" : "lz4f") << " large: " << n
+              << " -> " << *clen << " bytes\n";
+  }
+}
+
 
 // arrow pools over memory the front-end did not allocate: (a) malloc'd host memory pinned by
 // hipHostRegister (its device address may differ from the host one, so the device must stage
@@ -793,10 +830,13 @@ int main(int argc, char** argv) {
     PoolTests(std::string(argv[2]) == "1", argv[3]);
   } else if (argc >= 4 && mode == "arrow") {
     ArrowCodecTests(argv[2], argv[3]);
+  } else if (argc >= 4 && mode == "arrow_large") {
+    ArrowLargeTests(argv[2]);
   } else if (argc >= 4) {
     GpuTests(argv[2], argv[3]);
   } else {
-    std::cerr << "usage: frontend_test cpu | gpu <input> <outdir> | arrow <input> <outdir> | pool <0|1> <input>\n";
+    std::cerr << "usage: frontend_test cpu | gpu <input> <outdir> | arrow <input> <outdir> | "
+                 "arrow_large <input> <outdir> | pool <0|1> <input>\n";
     return 2;
   }
   std::cout << (g_failures ? "FAILED " : "PASSED ") << g_failures << " failures\n";

@@ -261,6 +261,23 @@ def test_arrow_codec_adapter_on_gpu(tmp_path):
 
 
 @pytest.mark.gpu
+def test_arrow_codec_adapter_above_1024_segments(tmp_path):
+    """An Arrow IPC body above 64 MiB is more than 1024 segments: the frame index behind
+    HipCodec::Compress (a prefix sum in tiles of 1024 entries) crosses a tile, and the adapter's
+    head + body + EndMark arithmetic meets compressed and raw LZ4 blocks (kind 1's random
+    regions).  The C++ side compresses 1025 segments and a 1-byte tail as ZSTD and as
+    LZ4_FRAME and compares the GPU decode and the stock Arrow decode with the input."""
+    if not os.path.exists(BIN):
+        _build()
+    inp = tmp_path / "input.bin"
+    inp.write_bytes(O.fill(1, 5, 1025 * 65536 + 1).tobytes())
+    r = subprocess.run([BIN, "arrow_large", str(inp), str(tmp_path)], capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "zstd large: 67174401 -> " in r.stdout and "lz4f large: 67174401 -> " in r.stdout
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("fmt,ipc", [("parquet", "none"), ("feather", "zstd"), ("raw", "none")])
 def test_demo_app_modes(tmp_path, fmt, ipc):
     """demo_app (reference apps/demo_app.cc): mode 1 reads a Parquet / Feather table and

@@ -276,6 +276,45 @@ def test_round_trip(eng, n):
             assert b"".join(blocks) == data
 
 
+def test_join_past_one_scan_tile(eng):
+    """1025 fragments: the join's prefix sum (scan_sizes_kernel, tiles of 1024 entries with a
+    carried base) crosses a tile border.  The expected stream is the model's join of the
+    engine's own 1025 slots, so the offsets, the length and every byte are pinned, and the
+    split and the joined decode return the input."""
+    n = 1024 * S.BLOCK + 1
+    nseg = S.nfrag(n)
+    assert nseg == 1025
+    data = eng.empty(n)
+    eng.fill(1, C.SEED, data)
+    slab, stride, sizes = eng.compress(codec(), data, S.BLOCK)
+    cap = n + 4 * nseg + 5
+    joined = eng.empty(cap)
+    offsets, length = Longs(nseg + 1), Longs(1)
+    eng.snappy_join(slab, stride, sizes, n, offsets.ptr, joined, cap, length.ptr)
+    eng.sync()
+    h_sizes = sizes.cpu().numpy().astype(np.uint32)
+    h_slab = slab.cpu().numpy()
+    streams = [h_slab[i * stride:i * stride + h_sizes[i]].tobytes() for i in range(nseg)]
+    want = S.join(streams, n)
+    bodies = [len(s) - M.preamble(s)[1] for s in streams]
+    assert [M.preamble(s)[0] for s in streams] == [S.BLOCK] * 1024 + [1]
+    assert offsets.values() == np.concatenate([[0], np.cumsum(bodies)]).astype(int).tolist()
+    (total,) = length.values()
+    assert total == len(want) == len(M.varint(n)) + sum(bodies)
+    assert joined[:total].cpu().numpy().tobytes() == want
+    starts, status = Longs(nseg + 1), G.GuardedWords(1, "cuda", "status")
+    eng.snappy_split(joined, total, n, starts.ptr, status.ptr)
+    out = eng.empty(n)
+    prod = eng.empty(nseg, dtype=torch.int32)
+    eng.decompress_joined_into(joined, total, n, starts.ptr, out, prod, capacity=n)
+    eng.sync()
+    status.check()
+    assert int(status.values()[0]) == S.OK
+    assert starts.values() == [len(M.varint(n)) + o for o in offsets.values()]
+    assert prod.cpu().tolist() == [S.BLOCK] * 1024 + [1]
+    assert torch.equal(out, data)
+
+
 def test_decode_refusals(eng):
     import bitar_amd as B
     data, own, _ = case(1, 65537)
