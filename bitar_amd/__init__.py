@@ -21,7 +21,8 @@ CODEC_SNAPPY = 6  # one raw Snappy stream per segment (the LZ4 parse; decodes st
 CODEC_RANS = 72   # order-0 rANS, 64 interleaved states per segment (its own format)
 # The column codecs: name -> (base id, high nibble of a stream's byte 0, element widths in bytes).
 # The id of a width is base + log2(width): CODEC_<NAME><8 * width>, e.g. CODEC_INTPACK32 = 10,
-# and any id of a family decodes all its widths.
+# and any id of a family decodes all its widths -- except RANSPLANE's, which decode their own
+# width alone (the decoder's LDS is sized by the width).
 #   INTPACK   frame-of-reference bit packing of integers
 #   FLTPACK   decimal-scaled bit packing of floats / doubles
 #   DICTPACK  per-segment dictionary + bit-packed indices
@@ -29,6 +30,7 @@ CODEC_RANS = 72   # order-0 rANS, 64 interleaved states per segment (its own for
 #   AUTOPACK  per segment the smallest of the applicable four above (no format of its own: any id
 #             decodes all of them)
 #   CASCADE   RUNPACK's runs, their values and lengths packed by INTPACK (no candidate of AUTOPACK)
+#   RANSPLANE RANS with one table per byte plane of the element (likewise; width 1 is CODEC_RANS)
 COLUMN_CODECS = {
     "INTPACK": (8, 4, (1, 2, 4, 8)),
     "FLTPACK": (16, 5, (4, 8)),
@@ -36,6 +38,7 @@ COLUMN_CODECS = {
     "RUNPACK": (32, 7, (1, 2, 4, 8, 16)),
     "AUTOPACK": (40, None, (1, 2, 4, 8, 16)),
     "CASCADE": (64, 8, (1, 2, 4, 8)),
+    "RANSPLANE": (80, 0xB, (2, 4, 8)),
 }
 _COLUMN_IDS = {name: {w: base + w.bit_length() - 1 for w in widths}
                for name, (base, _, widths) in COLUMN_CODECS.items()}
@@ -216,6 +219,11 @@ def codec_autopack(width):
 def codec_cascade(width):
     """the CASCADE codec id of an element width of 1, 2, 4 or 8 bytes"""
     return _column_codec("CASCADE", width)
+
+
+def codec_ransplane(width):
+    """the RANSPLANE codec id of an element width of 2, 4 or 8 bytes"""
+    return _column_codec("RANSPLANE", width)
 
 
 def max_distance(codec):

@@ -1,8 +1,9 @@
 // demo_app.cc -- the bitar demo/benchmark harness on MI355X (reference apps/demo_app.cc).
 //
-//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy|rans]
+//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy|rans|ransplane]
 //            [--seg N] [--devices N] [--workers N] [--ipc-codec none|zstd|lz4]
 //            [--filter shuffle|bitshuffle --element-width 2|4|8|16]
+//            (--codec ransplane takes --element-width 2|4|8 and no filter)
 //   demo_app --synthetic N ...      (no file: N bytes of a generated mixed buffer)
 //
 // ReadData (demo_app.cc:295-330):
@@ -317,6 +318,7 @@ int main(int argc, char** argv) {
                      : codec_name == "zstd" ? bitar::Codec::ZSTD
                      : codec_name == "snappy" ? bitar::Codec::SNAPPY
                      : codec_name == "rans" ? bitar::Codec::RANS
+                     : codec_name == "ransplane" ? bitar::Codec::RANSPLANE
                                             : bitar::Codec::DEFLATE;
   // a per-segment transposition of --element-width byte values in front of the codec
   if (filter_name != "none" && filter_name != "shuffle" && filter_name != "bitshuffle") {
@@ -339,6 +341,9 @@ int main(int argc, char** argv) {
     cfg->set_decompressed_seg_size32(seg);
     if (filter != bitar::Filter::NONE)
       cfg->set_filter(filter, static_cast<uint8_t>(std::min<uint32_t>(element_width, 255)));
+    // (RANSPLANE codes --element-width 2|4|8 byte planes itself and takes no filter)
+    else if (codec == bitar::Codec::RANSPLANE)
+      cfg->set_element_width(static_cast<uint8_t>(std::min<uint32_t>(element_width, 255)));
     cfg->set_max_preallocate_memzones(static_cast<uint16_t>(
         std::min<int64_t>(65535, host->size() / seg + 64)));
     auto st = d->Initialize(std::move(cfg));

@@ -2,8 +2,9 @@
 // reference user measures with demo_app's EvaluateSync (reference apps/demo_app.cc:332-357,
 // PrintPerfNumbers 82-89), as one JSON line for bench.py.
 //
-//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy|rans]
-//                  [--steps K] [--warmup W] [--no-host]
+//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy|rans|ransplane]
+//                  [--steps K] [--warmup W] [--no-host] [--element-width 2|4|8]
+//   (--element-width: the element of --codec ransplane, 4 by default)
 //
 // Leg "frontend": an HBM-resident arrow::Buffer of N bytes (the synthetic input of kind K,
 // generated on the device), K timed round trips of CompressDevice::Compress (qp 0) +
@@ -106,6 +107,7 @@ int main(int argc, char** argv) {
   int64_t n = int64_t{1} << 30;
   uint32_t seg = 65536;
   int kind = 1, steps = 10, warmup = 3;
+  uint32_t element_width = 4;
   bool host = true;
   std::string codec = "lz4";
   for (int i = 1; i < argc; ++i) {
@@ -118,6 +120,7 @@ int main(int argc, char** argv) {
     else if (a == "--warmup") warmup = std::stoi(next());
     else if (a == "--codec") codec = next();
     else if (a == "--no-host") host = false;
+    else if (a == "--element-width") element_width = static_cast<uint32_t>(std::stoul(next()));
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -137,7 +140,10 @@ int main(int argc, char** argv) {
   cfg->set_codec(codec == "zstd" ? bitar::Codec::ZSTD
                  : codec == "snappy" ? bitar::Codec::SNAPPY
                  : codec == "rans" ? bitar::Codec::RANS
+                 : codec == "ransplane" ? bitar::Codec::RANSPLANE
                  : codec == "deflate" ? bitar::Codec::DEFLATE : bitar::Codec::LZ4);
+  if (codec == "ransplane")
+    cfg->set_element_width(static_cast<uint8_t>(std::min<uint32_t>(element_width, 255)));
   cfg->set_decompressed_seg_size32(seg);
   // the slot pool holds a whole call's outputs from the start (no critical-path growth)
   cfg->set_max_preallocate_memzones(

@@ -66,12 +66,16 @@ using Class_HIP_GFX950 =
 /// interleaved states per segment, for bytes whose gain is their histogram and not their repeats
 /// -- non-decimal floats behind Filter::SHUFFLE or BITSHUFFLE, embeddings, noisy sensor words;
 /// one level, no window, no chained operations; filters and checksums as for LZ4.
+/// RANSPLANE is RANS with one table per byte plane of an element (likewise its own, DESIGN.md
+/// 4.26): bf16 / fp16 / fp32 / fp64 weights, activations and embeddings, whose exponent byte and
+/// low mantissa bytes have different histograms; element_width() is 2, 4 or 8 and, unlike the
+/// other column codecs, is needed on the decompressing side too; it takes no filter.
 /// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
 /// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
 /// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
-  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11
+  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11, RANSPLANE = 12
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
@@ -133,7 +137,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS have no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }
@@ -208,7 +212,9 @@ class HipConfiguration : public Configuration<Class_HIP_GFX950> {
   }
   /// The element width alone: what Codec::INTPACK (1, 2, 4 or 8 bytes), Codec::FLTPACK (4 or
   /// 8 bytes), Codec::DICTPACK (4, 8 or 16 bytes), Codec::RUNPACK and Codec::AUTOPACK (1, 2, 4,
-  /// 8 or 16 bytes) and Codec::CASCADE (1, 2, 4 or 8 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it.
+  /// 8 or 16 bytes), Codec::CASCADE (1, 2, 4 or 8 bytes) and Codec::RANSPLANE (2, 4 or 8 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it
+  /// -- except for Codec::RANSPLANE, whose decoder is the configured width's own and rejects
+  /// streams of another width.
   void set_element_width(std::uint8_t element_width) { element_width_ = element_width; }
 
   static HipConfiguration Defaults() { return {}; }

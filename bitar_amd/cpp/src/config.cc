@@ -18,6 +18,7 @@ std::string_view ToString(Codec c) {
     case Codec::SNAPPY: return "SNAPPY";
     case Codec::CASCADE: return "CASCADE";
     case Codec::RANS: return "RANS";
+    case Codec::RANSPLANE: return "RANSPLANE";
   }
   return "UNKNOWN";
 }

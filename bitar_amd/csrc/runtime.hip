@@ -24,6 +24,8 @@
 
 namespace bitar_hip {
 struct Rans;  // (rans.hip: the column kernels with the rANS format's traits)
+struct RansPlane;  // (ransplane.hip: the same per byte plane; a decoder per element width)
+template <uint32_t W> struct RansPlaneDecoder;
 template <uint32_t RING, uint32_t HLOG>
 __global__ void lz4_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
                                     uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
@@ -383,7 +385,7 @@ extern "C++" {
 //     nibble 4 + f -- INTPACK, FLTPACK, DICTPACK, RUNPACK -- which is what autopack_route_kernel
 //     writes.
 enum ColumnFamily : int {
-  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kColumnFamilies
+  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kColumnFamilies
 };
 struct ColumnRow {
   uint32_t base, nibble, widths;
@@ -395,6 +397,7 @@ constexpr ColumnRow kColumn[kColumnFamilies] = {
     {BITAR_HIP_CODEC_RUNPACK8, 7, 1 | 2 | 4 | 8 | 16},       // RUNPACK
     {BITAR_HIP_CODEC_AUTOPACK8, 0, 1 | 2 | 4 | 8 | 16},      // AUTOPACK
     {BITAR_HIP_CODEC_CASCADE8, 8, 1 | 2 | 4 | 8},            // CASCADE (no candidate of AUTOPACK)
+    {BITAR_HIP_CODEC_RANSPLANE16 - 1, 0xB, 2 | 4 | 8},       // RANSPLANE (likewise)
 };
 constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
 constexpr uint32_t kListedDecoders = 4;
@@ -444,6 +447,7 @@ static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
     case kDictPack: return width_kernel<bitar_hip::DictPack, kDictPack, STORE>(lg);
     case kRunPack: return width_kernel<bitar_hip::RunPack, kRunPack, true>(lg);
     case kCascade: return width_kernel<bitar_hip::Cascade, kCascade, true>(lg);
+    case kRansPlane: return width_kernel<bitar_hip::RansPlane, kRansPlane, true>(lg);
     default: return nullptr;
   }
 }
@@ -455,6 +459,15 @@ static DecompressKernel decompress_kernel(uint32_t f) {
     case kDictPack: return bitar_hip::column_decompress_kernel<bitar_hip::DictPack, LISTED>;
     case kCascade: return bitar_hip::column_decompress_kernel<bitar_hip::Cascade, LISTED>;
     default: return bitar_hip::column_decompress_kernel<bitar_hip::RunPack, LISTED>;
+  }
+}
+// RANSPLANE's decoders: one per element width (its LDS is the width's), and an id decodes its
+// own width alone
+static DecompressKernel ransplane_decompress_kernel(uint32_t lg) {
+  switch (lg) {
+    case 1: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<2>, false>;
+    case 2: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<4>, false>;
+    default: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<8>, false>;
   }
 }
 }  // extern "C++"
@@ -668,7 +681,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   const ColumnCodec cc = column_codec(codec);
   if (cc && cc.family != kAutoPack) {
     // one streaming kernel, the same work for every segment: plain order (intpack.hip,
-    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip)
+    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip)
     hipLaunchKernelGGL(compress_kernel<true>(cc.family, cc.lg), dim3((uint32_t)nseg), dim3(64), 0,
                        s, in, n, seg, slab, slot_stride, dsts, d_sizes);
   }
@@ -1117,9 +1130,11 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const auto* slab = static_cast<const uint8_t*>(d_slab);
   auto* out = static_cast<uint8_t*>(d_out);
   if (cc && cc.family != kAutoPack) {
-    hipLaunchKernelGGL(decompress_kernel<false>(cc.family), dim3(nseg), dim3(64), 0, s, srcs, slab,
-                       stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(cc.family == kRansPlane ? ransplane_decompress_kernel(cc.lg)
+                                               : decompress_kernel<false>(cc.family),
+                       dim3(nseg), dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out,
+                       d_produced, err_word(ctx, s), (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr);
   }
   else if (codec == BITAR_HIP_CODEC_RANS) {
     // (rans.hip: plain order, a segment's work is its length whatever its coded size)

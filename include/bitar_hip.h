@@ -288,7 +288,54 @@ enum bitar_hip_codec {
    * integrity check) after part of the segment's output range may have been written.  Nothing
    * outside that range is written.  Streams no encoder writes decode: any table that sums to
    * 4096, a rans form larger than 4 + L. */
-  BITAR_HIP_CODEC_RANS = 72
+  BITAR_HIP_CODEC_RANS = 72,
+  /* RANSPLANE: RANS with one order-0 table per byte plane of an element of
+   * w = 2, 4 or 8 bytes -- bf16 / fp16 / fp32 / fp64 weights, activations and embeddings, whose
+   * exponent byte has 2..3 bits of entropy and whose low mantissa bytes have 8, and integer
+   * columns with noisy low bytes.  No filter pass: 64 is a multiple of w, so lane i mod 64 codes
+   * plane i mod w for the whole segment.  No reference counterpart and no stock library reads the
+   * format (tests/ransplane_model.py is a numpy reader and writer).  The id is 80 + log2(w); 80
+   * itself is not offered (width 1 is RANS), and ids 73..79 and 84.. stay unknown.  Unlike the
+   * other families, an id decodes only its own width: the decoder's LDS is sized by w.
+   * One stream per segment of L bytes, w = 1 << lg:
+   *   byte 0      0xB0 | mode << 3 | lg      mode 0 planes, 1 stored; lg 1, 2 or 3
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                           size = 4 + L
+   *   planes:     bitmaps  w x 32 bytes, plane 0 first; in plane p's bitmap bit s (byte s >> 3,
+   *                        bit s & 7) is set iff byte value s occurs among the bytes i < L with
+   *                        i mod w == p (i counts from the segment's first byte, not its address)
+   *               freqs    w fields, plane 0 first, each exactly RANS's freqs field for that
+   *                        plane: f - 1 of the k-th present symbol in bits [12k, 12k + 12) of a
+   *                        little-endian bit string, zero-padded to an even number of bytes
+   *                        (tsize_p = 2 * ceil(12 * nsym_p / 16))
+   *               words    nw little-endian 16-bit words, in the order the encoder emitted them
+   *               states   64 x LE32, the encoder's final state of lane 0..63
+   *   size = 4 + 32 w + sum(tsize_p) + 2*nw + 256
+   * Frequencies, per plane: with n_p the number of bytes of plane p, c_p[s] their counts and
+   * nsym_p the number of present symbols, f_p[s] = 1 + floor(c_p[s] * (4096 - nsym_p) / n_p), and
+   * the deficit 4096 - sum(f_p) goes to the plane's most frequent symbol (the lowest value on a
+   * tie): RANS's rule with n_p in place of L.
+   * Coder: RANS's, word for word -- 64 states starting at 2^16, symbol i in lane i mod 64 at step
+   * i div 64, the encoder running backward and emitting x & 0xFFFF when x >= f * 2^20, a step's
+   * words in lane order, the decoder running forward and refilling from the end of `words` by
+   * ballot rank -- with the f and cum of plane i mod w.
+   * The planes form is taken iff L >= w (every plane non-empty) and its size is strictly below
+   * 4 + L; otherwise the segment is stored (tag 0xB8 | lg).  Neither L nor seg need be a multiple
+   * of w: there is no tail, the last planes are one byte shorter.
+   * The decoder rejects: a high nibble other than 0xB, lg other than that of the id it was called
+   * under, byte 1 != 0, L > seg, a stored form whose size is not 4 + L, a planes form with L < w,
+   * a stream too short for its bitmaps, tables and states, any plane's bitmap empty, any plane's
+   * frequencies not summing to 4096, non-zero pad bits in any plane's freqs field, a size for
+   * which 2*nw is negative or odd, an initial state below 2^16 -- all before the first output
+   * byte -- and a refill that needs more words than remain, words left over, or a final state
+   * other than 2^16 after part of the segment's output range may have been written.  Nothing is
+   * read outside the stream's bytes and nothing is written outside the segment's first L output
+   * bytes.  Streams no encoder writes decode: any tables that sum to 4096, a planes form larger
+   * than 4 + L. */
+  BITAR_HIP_CODEC_RANSPLANE16 = 81,
+  BITAR_HIP_CODEC_RANSPLANE32 = 82,
+  BITAR_HIP_CODEC_RANSPLANE64 = 83
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -299,6 +346,11 @@ enum bitar_hip_codec {
 /* The FLTPACK id of an element width of 4 (float) or 8 (double) bytes. */
 #define BITAR_HIP_CODEC_FLTPACK(width) \
   ((width) == 4 ? BITAR_HIP_CODEC_FLTPACK32 : BITAR_HIP_CODEC_FLTPACK64)
+
+/* The RANSPLANE id of an element width of 2, 4 or 8 bytes. */
+#define BITAR_HIP_CODEC_RANSPLANE(width) \
+  ((width) == 2 ? BITAR_HIP_CODEC_RANSPLANE16 : (width) == 4 ? BITAR_HIP_CODEC_RANSPLANE32 : \
+   BITAR_HIP_CODEC_RANSPLANE64)
 
 /* The DICTPACK id of an element width of 4, 8 or 16 bytes. */
 #define BITAR_HIP_CODEC_DICTPACK(width) \
@@ -373,14 +425,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE and RANS have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
