@@ -19,6 +19,7 @@ CODEC_DEFLATE_DYNAMIC = 4  # HuffmanEncoding::DYNAMIC (decoded as CODEC_DEFLATE)
 CODEC_LZ4_WIDE = 5  # LZ4 blocks from the wide parse (16 KiB history): the ratio operating point
 CODEC_SNAPPY = 6  # one raw Snappy stream per segment (the LZ4 parse; decodes stock raw Snappy)
 CODEC_RANS = 72   # order-0 rANS, 64 interleaved states per segment (its own format)
+CODEC_SYMTAB = 88  # per-segment symbol table for string data (its own format)
 # The column codecs: name -> (base id, high nibble of a stream's byte 0, element widths in bytes).
 # The id of a width is base + log2(width): CODEC_<NAME><8 * width>, e.g. CODEC_INTPACK32 = 10,
 # and any id of a family decodes all its widths -- except RANSPLANE's, which decode their own

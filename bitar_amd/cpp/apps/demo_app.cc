@@ -1,6 +1,6 @@
 // demo_app.cc -- the bitar demo/benchmark harness on MI355X (reference apps/demo_app.cc).
 //
-//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy|rans|ransplane]
+//   demo_app --file|-f PATH [--bytes|-b N] [--mode|-m 0|1] [--codec deflate|lz4|zstd|snappy|rans|ransplane|symtab]
 //            [--seg N] [--devices N] [--workers N] [--ipc-codec none|zstd|lz4]
 //            [--filter shuffle|bitshuffle --element-width 2|4|8|16]
 //            (--codec ransplane takes --element-width 2|4|8 and no filter)
@@ -319,6 +319,7 @@ int main(int argc, char** argv) {
                      : codec_name == "snappy" ? bitar::Codec::SNAPPY
                      : codec_name == "rans" ? bitar::Codec::RANS
                      : codec_name == "ransplane" ? bitar::Codec::RANSPLANE
+                     : codec_name == "symtab" ? bitar::Codec::SYMTAB
                                             : bitar::Codec::DEFLATE;
   // a per-segment transposition of --element-width byte values in front of the codec
   if (filter_name != "none" && filter_name != "shuffle" && filter_name != "bitshuffle") {

@@ -2,7 +2,7 @@
 // reference user measures with demo_app's EvaluateSync (reference apps/demo_app.cc:332-357,
 // PrintPerfNumbers 82-89), as one JSON line for bench.py.
 //
-//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy|rans|ransplane]
+//   frontend_bench [--bytes N] [--seg N] [--kind K] [--codec lz4|deflate|zstd|snappy|rans|ransplane|symtab]
 //                  [--steps K] [--warmup W] [--no-host] [--element-width 2|4|8]
 //   (--element-width: the element of --codec ransplane, 4 by default)
 //
@@ -141,6 +141,7 @@ int main(int argc, char** argv) {
                  : codec == "snappy" ? bitar::Codec::SNAPPY
                  : codec == "rans" ? bitar::Codec::RANS
                  : codec == "ransplane" ? bitar::Codec::RANSPLANE
+                 : codec == "symtab" ? bitar::Codec::SYMTAB
                  : codec == "deflate" ? bitar::Codec::DEFLATE : bitar::Codec::LZ4);
   if (codec == "ransplane")
     cfg->set_element_width(static_cast<uint8_t>(std::min<uint32_t>(element_width, 255)));

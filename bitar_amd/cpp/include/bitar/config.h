@@ -70,12 +70,16 @@ using Class_HIP_GFX950 =
 /// 4.26): bf16 / fp16 / fp32 / fp64 weights, activations and embeddings, whose exponent byte and
 /// low mantissa bytes have different histograms; element_width() is 2, 4 or 8 and, unlike the
 /// other column codecs, is needed on the decompressing side too; it takes no filter.
+/// SYMTAB is the engine's per-segment symbol table (likewise its own), in the
+/// style of FSST: up to 255 strings of 1..8 bytes, the text written as one-byte codes -- the data
+/// buffer of a string or binary column (names, URLs, log lines, keys); a byte codec with no element
+/// width, one level, no window, no chained operations; filters and checksums as for LZ4.
 /// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
 /// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
 /// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
-  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11, RANSPLANE = 12
+  AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11, RANSPLANE = 12, SYMTAB = 13
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
@@ -137,7 +141,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE have no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE and SYMTAB have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }

@@ -342,6 +342,7 @@ std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     case Codec::SNAPPY: return BITAR_HIP_CODEC_SNAPPY;
     case Codec::RANS: return BITAR_HIP_CODEC_RANS;
+    case Codec::SYMTAB: return BITAR_HIP_CODEC_SYMTAB;
     default:
       return c.huffman_enc() == HuffmanEncoding::FIXED ? BITAR_HIP_CODEC_DEFLATE
                                                       : BITAR_HIP_CODEC_DEFLATE_DYNAMIC;
@@ -807,7 +808,7 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
     return arrow::Status::Invalid("Burst size must be greater than 0");
   if (configuration_->codec() != Codec::DEFLATE && configuration_->codec() != Codec::LZ4 &&
       configuration_->codec() != Codec::ZSTD && configuration_->codec() != Codec::SNAPPY &&
-      configuration_->codec() != Codec::RANS &&
+      configuration_->codec() != Codec::RANS && configuration_->codec() != Codec::SYMTAB &&
       !internal::IsColumnCodec(configuration_->codec()))
     return arrow::Status::NotImplemented("Compress device ", +device_id_,
                                          " does not support the codec");
@@ -838,6 +839,10 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   if (configuration_->codec() == Codec::RANS && configuration_->max_sgl_segs() > 1)
     return arrow::Status::Invalid("RANS cannot be combined with chained operations "
                                   "(max_sgl_segs > 1)");
+  // (and for SYMTAB: one stream is one segment's table and codes)
+  if (configuration_->codec() == Codec::SYMTAB && configuration_->max_sgl_segs() > 1)
+    return arrow::Status::Invalid("SYMTAB cannot be combined with chained operations "
+                                  "(max_sgl_segs > 1)");
   // level: LZ4 1..9 (>= 2 selects the wide parse); the other codecs have one level, so any
   // other value is refused rather than ignored (the reference always sets 1)
   if (configuration_->level() < 1 || configuration_->level() > 9)
@@ -857,8 +862,9 @@ arrow::Status CompressDevice<Class, Enable>::ValidateConfiguration() {
   while ((1u << window) < reach) ++window;
   encoder_window_ = window;
   const std::uint8_t max_window = configuration_->codec() == Codec::DEFLATE ? 15 : 16;
-  // (a column codec and RANS have no matches and no window: ignored, reported 0)
-  if (internal::IsColumnCodec(configuration_->codec()) || configuration_->codec() == Codec::RANS) {
+  // (a column codec, RANS and SYMTAB have no matches and no window: ignored, reported 0)
+  if (internal::IsColumnCodec(configuration_->codec()) || configuration_->codec() == Codec::RANS ||
+      configuration_->codec() == Codec::SYMTAB) {
     encoder_window_ = 0;
     configuration_->set_window_size(0);
   } else if (configuration_->window_size() == 0) {

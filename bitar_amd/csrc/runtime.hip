@@ -26,6 +26,7 @@ namespace bitar_hip {
 struct Rans;  // (rans.hip: the column kernels with the rANS format's traits)
 struct RansPlane;  // (ransplane.hip: the same per byte plane; a decoder per element width)
 template <uint32_t W> struct RansPlaneDecoder;
+struct SymTab;  // (symtab.hip: the same with the symbol-table format's traits)
 template <uint32_t RING, uint32_t HLOG>
 __global__ void lz4_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
                                     uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
@@ -495,7 +496,7 @@ uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
     bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
   else if (codec == BITAR_HIP_CODEC_SNAPPY)
     bound = (uint64_t)seg + 6u;                         // the stored form: varint + tag + segment
-  else if (codec == BITAR_HIP_CODEC_RANS)
+  else if (codec == BITAR_HIP_CODEC_RANS || codec == BITAR_HIP_CODEC_SYMTAB)
     bound = (uint64_t)seg + 4u;                         // the stored form, as the column codecs'
   else if (codec == BITAR_HIP_CODEC_DEFLATE || codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC)
     bound = ((uint64_t)seg * 9 + 7) / 8 + 16u;          // fixed Huffman, 9 bits/literal
@@ -654,7 +655,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
       codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
       codec != BITAR_HIP_CODEC_LZ4_WIDE && codec != BITAR_HIP_CODEC_SNAPPY &&
-      codec != BITAR_HIP_CODEC_RANS && !column_codec(codec))
+      codec != BITAR_HIP_CODEC_RANS && codec != BITAR_HIP_CODEC_SYMTAB && !column_codec(codec))
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
@@ -689,6 +690,13 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
     // the same again (rans.hip): histogram, table and coder of one segment in one wave; a
     // segment never fails (the stored form fits every slot)
     hipLaunchKernelGGL((bitar_hip::column_compress_kernel<bitar_hip::Rans, 1, true>),
+                       dim3((uint32_t)nseg), dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts,
+                       d_sizes);
+  }
+  else if (codec == BITAR_HIP_CODEC_SYMTAB) {
+    // and again (symtab.hip): the table's five generations and the parse of one segment in one
+    // wave; a segment never fails (the stored form fits every slot)
+    hipLaunchKernelGGL((bitar_hip::column_compress_kernel<bitar_hip::SymTab, 1, true>),
                        dim3((uint32_t)nseg), dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts,
                        d_sizes);
   }
@@ -1108,7 +1116,7 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   const ColumnCodec cc = column_codec(codec);
   if (!cc &&
       codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_SNAPPY &&
-      codec != BITAR_HIP_CODEC_RANS &&
+      codec != BITAR_HIP_CODEC_RANS && codec != BITAR_HIP_CODEC_SYMTAB &&
       codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
     return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (nseg == 0) return 0;  // reference device.cc:244-246
@@ -1139,6 +1147,12 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
   else if (codec == BITAR_HIP_CODEC_RANS) {
     // (rans.hip: plain order, a segment's work is its length whatever its coded size)
     hipLaunchKernelGGL((bitar_hip::column_decompress_kernel<bitar_hip::Rans, false>), dim3(nseg),
+                       dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out, d_produced,
+                       err_word(ctx, s), (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+  }
+  else if (codec == BITAR_HIP_CODEC_SYMTAB) {
+    // (symtab.hip: plain order too)
+    hipLaunchKernelGGL((bitar_hip::column_decompress_kernel<bitar_hip::SymTab, false>), dim3(nseg),
                        dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out, d_produced,
                        err_word(ctx, s), (const uint32_t*)nullptr, (const uint32_t*)nullptr);
   }

@@ -335,7 +335,49 @@ enum bitar_hip_codec {
    * than 4 + L. */
   BITAR_HIP_CODEC_RANSPLANE16 = 81,
   BITAR_HIP_CODEC_RANSPLANE32 = 82,
-  BITAR_HIP_CODEC_RANSPLANE64 = 83
+  BITAR_HIP_CODEC_RANSPLANE64 = 83,
+  /* SYMTAB: a static symbol table per segment, in the style of FSST, for the
+   * data buffer of a string or binary column -- names, URLs, log lines, keys: up to 255 byte
+   * strings of 1..8 bytes, the text written as one-byte codes, anything else escaped.  No
+   * reference counterpart and no stock library reads the format (tests/symtab_model.py is a
+   * Python reader and writer).  A byte codec: no element width.  Ids 84..87 are left for
+   * RANSPLANE.  One stream per segment of L bytes, 1..65536:
+   *   byte 0      0xC0 | mode            mode 0 coded, 1 stored
+   *   byte 1      nsym, 1..255           (0 in the stored form)
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                     size = 4 + L
+   *   coded:      LE16 nc                number of codes, >= 1
+   *               lens[nsym]             one byte each, 1..8
+   *               syms                   the symbols' bytes, concatenated in code order
+   *               codes[nc]              c < nsym: symbol c;  255: the next unread byte of lits
+   *               lits[nx]               nx = the number of codes equal to 255
+   *   size = 6 + nsym + sum(lens) + nc + nx
+   * Escapes sit in a stream of their own, so every byte of `codes` is a code: a code's output
+   * offset is a prefix sum of lengths, an escape's literal index its rank among the escapes.
+   * The coded form is taken iff it is strictly smaller than 4 + L.  The decoder rejects a high
+   * nibble other than 0xC, a mode above 1, byte 1 other than 0 when stored, L > seg, nsym = 0 or
+   * nc = 0 when coded, a length of 0 or above 8, a code in [nsym, 255), a stream whose size is not
+   * exactly the formula, and lengths that do not sum to exactly L (an escape counts 1) -- all
+   * before the first output byte -- and decodes everything else; duplicate symbols are allowed.
+   * Nothing outside the segment's L output bytes is written, nothing outside the stream is read.
+   * The encoder's rule (its bytes are the model's):
+   * Sample: the segment is cut into chunks of 256 bytes (the last may be short); the sample is
+   * all chunks when L <= 16384 and those whose index is a multiple of 4 otherwise (at most 64).
+   * Nothing is matched or paired across a chunk's end.
+   * Items: ids 0..255 are the byte values, id 256 + c is symbol c of the current table T.
+   * Generations: T starts empty; in each of five generations every sample chunk is parsed
+   * greedily against T -- at a position the longest symbol of T that matches inside the chunk,
+   * else the single byte -- and c1[x] counts the parsed items.  An adjacent pair (x, y) of a chunk
+   * with len(x) + len(y) <= 8 has key = x * 512 + y and slot = (key * 0x9E3779B1 mod 2^32) >> 20
+   * (4096 slots); of the keys that share a slot in a generation only the smallest is counted.
+   * Selection: the candidates are, in index order, the items with c1 > 0 (index = id, gain =
+   * c1 * len) and the occupied slots (index = 512 + slot, gain = count * total length).  With 255
+   * or fewer all are taken; otherwise, thr being the 255th largest gain, every candidate with
+   * gain > thr and then those with gain = thr in index order until 255 are.  The new T is the
+   * taken candidates in index order; after the fifth generation a symbol's code is its position.
+   * Emit: the whole segment parsed greedily with T, no match passing its end; a symbol gives its
+   * code, a single byte not in T gives 255 in codes and the byte in lits. */
+  BITAR_HIP_CODEC_SYMTAB = 88
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -425,14 +467,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE and SYMTAB, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS and RANSPLANE have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE and SYMTAB have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
