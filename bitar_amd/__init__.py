@@ -483,6 +483,14 @@ class Engine:
         out["other"] = nseg - int(known.sum())
         return out
 
+    def lz4_chain(self, src, src_len, blocks, nblocks, out, capacity, produced, stream=None):
+        """the linked blocks of one LZ4 frame, in order on one wavefront (bitar_hip_lz4_chain):
+        blocks = nblocks pairs {offset in src, size | 1 << 31 when stored} of uint32 in HBM;
+        produced[0] receives the size or SEGMENT_ERROR (then the next sync raises IOError)"""
+        check(lib().bitar_hip_lz4_chain(self.ctx, self._stream(stream), _ptr(src), src_len,
+                                        _ptr(blocks), nblocks, _ptr(out), capacity,
+                                        _ptr(produced)))
+
     def sync(self, stream=None):
         s = self._stream(stream) if stream is not False else None
         check(lib().bitar_hip_sync(self.ctx, s))

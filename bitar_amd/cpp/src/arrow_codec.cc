@@ -23,6 +23,7 @@ namespace {
 
 constexpr uint32_t kSeg = 65536;  // segment = Zstd frame content = LZ4 frame block
 constexpr uint32_t kZstdMagic = 0xFD2FB528u, kLz4fMagic = 0x184D2204u;
+constexpr uint32_t kSkippableMagic = 0x184D2A50u;  // ..5F: skippable frames of both formats
 
 uint32_t Rd32(const uint8_t* p) {
   return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
@@ -269,8 +270,12 @@ arrow::Result<std::vector<Frame>> HipCodec::WalkZstd(const uint8_t* p, uint64_t 
   while (pos < n) {
     Frame f;
     f.offset = pos;
-    if (n - pos < 6 || Rd32(p + pos) != kZstdMagic)
-      return arrow::Status::NotImplemented("not a Zstandard frame at offset ", pos);
+    if (n - pos < 4) return arrow::Status::Invalid("truncated Zstandard frame header");
+    if ((Rd32(p + pos) & 0xFFFFFFF0u) == kSkippableMagic)
+      return arrow::Status::NotImplemented("skippable frame at offset ", pos);
+    if (Rd32(p + pos) != kZstdMagic)
+      return arrow::Status::Invalid("not a Zstandard frame at offset ", pos);
+    if (n - pos < 6) return arrow::Status::Invalid("truncated Zstandard frame header");
     pos += 4;
     const uint32_t fhd = p[pos++];
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1u, did_flag = fhd & 3u;
@@ -308,20 +313,29 @@ arrow::Result<std::vector<Frame>> HipCodec::WalkLz4f(const uint8_t* p, uint64_t 
   while (pos < n) {
     Frame f;
     f.offset = pos;
-    if (n - pos < 7 || Rd32(p + pos) != kLz4fMagic)
-      return arrow::Status::NotImplemented("not an LZ4 frame at offset ", pos);
+    if (n - pos < 4) return arrow::Status::Invalid("truncated LZ4 frame header");
+    if ((Rd32(p + pos) & 0xFFFFFFF0u) == kSkippableMagic)
+      return arrow::Status::NotImplemented("skippable frame at offset ", pos);
+    if (Rd32(p + pos) != kLz4fMagic)
+      return arrow::Status::Invalid("not an LZ4 frame at offset ", pos);
+    if (n - pos < 7) return arrow::Status::Invalid("truncated LZ4 frame header");
+    // Everything the format forbids is Invalid before anything this codec leaves out is
+    // NotImplemented: a frame that no reader takes is never called a missing feature.
     const uint32_t flg = p[pos + 4], bd = p[pos + 5];
     if ((flg >> 6) != 1) return arrow::Status::Invalid("LZ4 frame version");
+    if (flg & 2u) return arrow::Status::Invalid("LZ4 frame with a reserved FLG bit set");
+    if (bd & 0x8Fu) return arrow::Status::Invalid("LZ4 frame with a reserved BD bit set");
+    if (((bd >> 4) & 7) < 4) return arrow::Status::Invalid("LZ4 block size id below 4");
     f.linked = !((flg >> 5) & 1);
     const bool block_cks = (flg >> 4) & 1;
     f.content_checksum = (flg >> 2) & 1;
-    if (flg & 1) return arrow::Status::NotImplemented("LZ4 dictionary id");
-    if (((bd >> 4) & 7) != 4) return arrow::Status::NotImplemented("LZ4 blocks larger than 64 KiB");
-    const bool has_size = (flg >> 3) & 1;
-    const uint64_t dlen = 2 + (has_size ? 8 : 0);
+    const bool has_size = (flg >> 3) & 1, has_dict = flg & 1;
+    const uint64_t dlen = 2 + (has_size ? 8 : 0) + (has_dict ? 4 : 0);
     if (pos + 4 + dlen + 1 > n) return arrow::Status::Invalid("truncated LZ4 frame header");
     if (((Xxh32(p + pos + 4, dlen, 0) >> 8) & 0xFF) != p[pos + 4 + dlen])
       return arrow::Status::Invalid("LZ4 frame header checksum");
+    if (has_dict) return arrow::Status::NotImplemented("LZ4 dictionary id");
+    if (((bd >> 4) & 7) != 4) return arrow::Status::NotImplemented("LZ4 blocks larger than 64 KiB");
     if (has_size) {
       f.has_content = true;
       for (int k = 0; k < 8; ++k) f.content |= uint64_t(p[pos + 6 + k]) << (8 * k);
@@ -339,7 +353,9 @@ arrow::Result<std::vector<Frame>> HipCodec::WalkLz4f(const uint8_t* p, uint64_t 
         if (Xxh32(p + pos, len, 0) != Rd32(p + pos + len))
           return arrow::Status::IOError("LZ4 block checksum mismatch");
       }
-      f.blocks.push_back({pos, len, 0, (bs >> 31) != 0});
+      // (a stored block of no bytes, 0x80000000, is valid and is nothing to decode: dropped
+      // here, so that neither block mode sees it)
+      if (len) f.blocks.push_back({pos, len, 0, (bs >> 31) != 0});
       pos += len + (block_cks ? 4 : 0);
     }
     if (f.content_checksum) {
@@ -545,10 +561,15 @@ arrow::Result<int64_t> HipCodec::DecompressLz4f(const std::vector<Frame>& frames
       ARROW_RETURN_NOT_OK(Reserve(d_srcs_, c_srcs_, tab.size() * 4));
       ARROW_RETURN_NOT_OK(Reserve(d_off_, c_off_, 4));
       ARROW_RETURN_NOT_OK(Copy(d_srcs_, tab.data(), tab.size() * 4));
+      // The kernel has no per-block output limit (liblz4: 64 KiB); the frame as a whole gets
+      // 64 KiB per block, and never more than the caller's buffer plus the slack reserved
+      // above: a bound the stream and the caller set, not what earlier calls left in d_out_.
+      const uint64_t room = std::min<uint64_t>(
+          {f.blocks.size() * uint64_t{kSeg}, cap + kSeg - total, c_out_ - total});
       BITAR_ABI(bitar_hip_lz4_chain(ctx_, nullptr, d_in + f.offset, static_cast<uint32_t>(f.csize),
                                     static_cast<const uint32_t*>(d_srcs_),
-                                    static_cast<uint32_t>(f.blocks.size()), dout + total,
-                                    c_out_ - total, static_cast<uint32_t*>(d_off_)),
+                                    static_cast<uint32_t>(f.blocks.size()), dout + total, room,
+                                    static_cast<uint32_t*>(d_off_)),
                 "bitar_hip_lz4_chain");
       ARROW_RETURN_NOT_OK(Sync());
       uint32_t prod = 0;

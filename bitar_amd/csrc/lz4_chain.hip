@@ -34,8 +34,10 @@ __global__ __launch_bounds__(64) void lz4_chain_kernel(const uint8_t* __restrict
   s.fenced = 0;
   s.wb = ~0ull;
   s.wlen = 0;
-  auto lits = [&](uint32_t n) __attribute__((always_inline)) {
-    if (n >= kLongLit) literals_long(s, win, ring, n);
+  // `more`: output follows the run.  The table decides that, not the run's place in src (the
+  // blocks of a table need not lie in src in table order).
+  auto lits = [&](uint32_t n, bool more) __attribute__((always_inline)) {
+    if (n >= kLongLit) literals_long(s, win, ring, n, more);
     else if (n) literals_short(s, win, ring, n);
   };
   bool ok = true;
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(64) void lz4_chain_kernel(const uint8_t* __restrict
         ok = false;
         break;
       }
-      lits(bsz);
+      lits(bsz, b + 1 < nblocks);
       continue;
     }
     for (;;) {
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(64) void lz4_chain_kernel(const uint8_t* __restrict
         ok = false;
         break;
       }
-      lits(ll);
+      lits(ll, b + 1 < nblocks || s.ip + ll < end);
       if (s.ip == end) break;  // the block's last sequence: literals only
       if (s.ip + 2 > end) {
         ok = false;

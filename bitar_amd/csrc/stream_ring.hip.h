@@ -157,13 +157,13 @@ __device__ __forceinline__ void literals_short(State& s, uint8_t* win, uint8_t* 
   }
 }
 
+// `more`: output follows this run, so the ring must hold the run's end
 __device__ __forceinline__ void literals_long(State& s, uint8_t* win, uint8_t* ring,
-                                              uint32_t n) {
+                                              uint32_t n, bool more) {
   const uint32_t lane = lane_id();
   const uintptr_t base = (uintptr_t)s.dst;
   flush(s, ring, s.op, true);
   wave_copy_global(s.dst + s.op, s.src + s.ip, n);
-  const bool more = s.ip + n < s.csize;
   if (more) {
     // Seed the ring with the run's last kRing bytes so the ring stays hole-free: every
     // match with off <= kNearOff then finds its history in LDS.
@@ -183,6 +183,12 @@ __device__ __forceinline__ void literals_long(State& s, uint8_t* win, uint8_t* r
   s.ip += n;
   s.op += n;
   s.flushed = s.op;  // written straight to HBM (not yet fenced)
+}
+
+// one stream read front to back: output follows while stream does
+__device__ __forceinline__ void literals_long(State& s, uint8_t* win, uint8_t* ring,
+                                              uint32_t n) {
+  literals_long(s, win, ring, n, s.ip + n < s.csize);
 }
 
 // out[op, op+m) <- out[op-off, ...) with LZ4 overlap semantics: byte t copies

@@ -587,7 +587,8 @@ int bitar_hip_pack(bitar_hip_ctx* ctx, void* stream, const void* d_slab, uint64_
 /* LZ4 frame with LINKED blocks (LZ4 frame format Block_Independence = 0, the liblz4 and
  * Arrow LZ4_FRAME default): the blocks of ONE frame decode in order on one wavefront, each
  * block's matches reaching into the output of the blocks before it.  d_blocks holds nblocks
- * pairs {offset of the block's data in d_src, size | 1u << 31 for a stored block}; the
+ * pairs {offset of the block's data in d_src, size | 1u << 31 for a stored block}, decoded
+ * in table order wherever they lie in d_src; the
  * output goes to d_out (capacity bytes) and *d_produced receives its total size, or
  * BITAR_HIP_SEGMENT_ERROR (then the next sync returns BITAR_HIP_IO_ERROR).  Asynchronous on
  * `stream`.  Frame / block checksums are the caller's (XXH32).  Used by the Arrow util::Codec
