@@ -32,6 +32,7 @@ CODEC_SYMTAB = 88  # per-segment symbol table for string data (its own format, D
 #             decodes all of them)
 #   CASCADE   RUNPACK's runs, their values and lengths packed by INTPACK (no candidate of AUTOPACK)
 #   RANSPLANE RANS with one table per byte plane of the element (likewise; width 1 is CODEC_RANS)
+#   PATCHPACK INTPACK with per-miniblock exceptions for outliers (likewise)
 COLUMN_CODECS = {
     "INTPACK": (8, 4, (1, 2, 4, 8)),
     "FLTPACK": (16, 5, (4, 8)),
@@ -40,6 +41,7 @@ COLUMN_CODECS = {
     "AUTOPACK": (40, None, (1, 2, 4, 8, 16)),
     "CASCADE": (64, 8, (1, 2, 4, 8)),
     "RANSPLANE": (80, 0xB, (2, 4, 8)),
+    "PATCHPACK": (104, 9, (1, 2, 4, 8)),
 }
 _COLUMN_IDS = {name: {w: base + w.bit_length() - 1 for w in widths}
                for name, (base, _, widths) in COLUMN_CODECS.items()}
@@ -220,6 +222,11 @@ def codec_autopack(width):
 def codec_cascade(width):
     """the CASCADE codec id of an element width of 1, 2, 4 or 8 bytes"""
     return _column_codec("CASCADE", width)
+
+
+def codec_patchpack(width):
+    """the PATCHPACK codec id of an element width of 1, 2, 4 or 8 bytes"""
+    return _column_codec("PATCHPACK", width)
 
 
 def codec_ransplane(width):

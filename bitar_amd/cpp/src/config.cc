@@ -19,6 +19,7 @@ std::string_view ToString(Codec c) {
     case Codec::CASCADE: return "CASCADE";
     case Codec::RANS: return "RANS";
     case Codec::RANSPLANE: return "RANSPLANE";
+    case Codec::PATCHPACK: return "PATCHPACK";
     case Codec::SYMTAB: return "SYMTAB";
   }
   return "UNKNOWN";

@@ -1,7 +1,8 @@
-// bitpack.hip.h -- what the bit-packing codecs share (intpack.hip, fltpack.hip, cascade.hip;
-// gfx950, wave64): wave reductions over DPP, element loads and stores at any alignment, the
-// payload emitter that writes a miniblock's bit string as aligned dwords, and INTPACK's plan and
-// miniblock decode over elements from anywhere (intpack.hip, cascade.hip).
+// bitpack.hip.h -- what the bit-packing codecs share (intpack.hip, fltpack.hip, cascade.hip,
+// patchpack.hip; gfx950, wave64): wave reductions over DPP, element loads and stores at any
+// alignment, the payload emitter that writes a miniblock's bit string as aligned dwords, the
+// exception lists' rank and position check (fltpack.hip, patchpack.hip), and INTPACK's plan and
+// miniblock decode over elements from anywhere (intpack.hip, cascade.hip, patchpack.hip).
 //
 // Payload of a miniblock of 64 elements at width b: 8 * b bytes, element t at bits
 // [t*b, (t+1)*b) of the little-endian bit string.  Lane t holds element t.
@@ -230,6 +231,51 @@ __device__ __forceinline__ typename Elem<W>::U extract_field(const GMEM uint8_t*
     if (b < 32) r &= (1u << b) - 1;
   }
   return r;
+}
+
+// ---- exceptions: elements kept raw behind the payload, pos[] (LE16, increasing) and val[] -----
+// (fltpack.hip: the values that are no decimal; patchpack.hip: the residuals too long to pack.)
+
+// the set bits of a wave mask below this lane: an exception's rank among its miniblock's
+__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                   __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The decoder's check of a position list, 64 at a time with neighbours across lanes: each of
+// the nx LE16 positions at pos is below m and above the one before.  sink(p) gets every position
+// p < m, from its lane, whether or not the list turns out valid; false for a list that must be
+// rejected.  Nothing is written but what the sink writes.
+template <class SINK>
+__device__ __forceinline__ bool check_positions(const GMEM uint8_t* pos, uint32_t nx, uint32_t m,
+                                                SINK&& sink) {
+  const uint32_t lane = lane_id();
+  bool bad = false;
+  uint32_t last = 0;
+  for (uint32_t j0 = 0; j0 < nx; j0 += kWave) {
+    const uint32_t j = j0 + lane;
+    uint32_t p = 0;
+    if (j < nx) p = pos[2 * j] | (uint32_t)pos[2 * j + 1] << 8;
+    uint32_t before = wave_shr1(p);
+    if (lane == 0) before = last;
+    if (j < nx) {
+      bad = bad || p >= m || (j > 0 && p <= before);
+      if (p < m) sink(p);
+    }
+    last = readlane(p, 63);  // (used only when a full chunk came before)
+  }
+  return ballot(bad) == 0;
+}
+
+// ... into a bitmap in LDS (zeroed by the caller up to bit m): bit p = element p is an exception
+__device__ __forceinline__ bool mark_positions(const GMEM uint8_t* pos, uint32_t nx, uint32_t m,
+                                               uint32_t* exc) {
+  return check_positions(pos, nx, m, [&](uint32_t p) { atomicOr(&exc[p >> 5], 1u << (p & 31u)); });
+}
+
+// the 64 bits of miniblock k in the bitmap: bit t = this miniblock's element t is an exception
+__device__ __forceinline__ uint64_t exception_mask(const uint32_t* exc, uint32_t k) {
+  return (uint64_t)uniform(exc[2 * k + 1]) << 32 | uniform(exc[2 * k]);
 }
 
 // ---- INTPACK's plan and its miniblock decode, over elements from anywhere ---------------------

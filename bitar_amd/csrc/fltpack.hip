@@ -74,11 +74,6 @@ __device__ __forceinline__ bool to_int(typename Elem<W>::U bits, double P,
   return in && from_int<W>(n, P) == bits;
 }
 
-__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {  // set bits below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                   __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 struct Shared {
   __attribute__((aligned(8))) uint8_t sample[kMaxSample * 4];  // every 16th element
   __attribute__((aligned(8))) uint8_t ref[kMaxMiniF * 2];      // references, W bytes each
@@ -273,20 +268,7 @@ __device__ __forceinline__ bool decompress_packed(const GMEM uint8_t* src, uint3
 
   // positions: each below m and above the one before (chunks of 64, neighbours across lanes)
   const uint32_t pos_at = pay_at + run, val_at = pos_at + 2 * nx;
-  uint32_t last = 0;
-  for (uint32_t j0 = 0; j0 < nx; j0 += kWave) {
-    const uint32_t j = j0 + lane;
-    uint32_t p = 0;
-    if (j < nx) p = src[pos_at + 2 * j] | (uint32_t)src[pos_at + 2 * j + 1] << 8;
-    uint32_t before = wave_shr1(p);
-    if (lane == 0) before = last;
-    if (j < nx) {
-      bad = bad || p >= m || (j > 0 && p <= before);
-      if (p < m) atomicOr(&sh.exc[p >> 5], 1u << (p & 31u));
-    }
-    last = readlane(p, 63);  // (used only when a full chunk came before)
-  }
-  if (ballot(bad) != 0) return false;
+  if (!mark_positions(src + pos_at, nx, m, sh.exc)) return false;
   lds_order();
 
   const double P = kPow10[e];
@@ -299,8 +281,7 @@ __device__ __forceinline__ bool decompress_packed(const GMEM uint8_t* src, uint3
     if (b) r = extract_field<W>(pay + sh.off[k], b);
     const U ref = load_elem<W>(src + ref_at + (k / 4) * W);
     U v = from_int<W>((S)(U)(r + ref), P);
-    const uint64_t mask =
-        (uint64_t)uniform(sh.exc[2 * k + 1]) << 32 | uniform(sh.exc[2 * k]);
+    const uint64_t mask = exception_mask(sh.exc, k);
     if (mask) {
       if ((mask >> lane) & 1u) v = load_elem<W>(src + val_at + (xi + rank_in(mask)) * W);
       xi += (uint32_t)__popcll(mask);

@@ -386,7 +386,8 @@ extern "C++" {
 //     nibble 4 + f -- INTPACK, FLTPACK, DICTPACK, RUNPACK -- which is what autopack_route_kernel
 //     writes.
 enum ColumnFamily : int {
-  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kColumnFamilies
+  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kPatchPack,
+  kColumnFamilies
 };
 struct ColumnRow {
   uint32_t base, nibble, widths;
@@ -399,6 +400,7 @@ constexpr ColumnRow kColumn[kColumnFamilies] = {
     {BITAR_HIP_CODEC_AUTOPACK8, 0, 1 | 2 | 4 | 8 | 16},      // AUTOPACK
     {BITAR_HIP_CODEC_CASCADE8, 8, 1 | 2 | 4 | 8},            // CASCADE (no candidate of AUTOPACK)
     {BITAR_HIP_CODEC_RANSPLANE16 - 1, 0xB, 2 | 4 | 8},       // RANSPLANE (likewise)
+    {BITAR_HIP_CODEC_PATCHPACK8, 9, 1 | 2 | 4 | 8},          // PATCHPACK (likewise)
 };
 constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
 constexpr uint32_t kListedDecoders = 4;
@@ -449,6 +451,7 @@ static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
     case kRunPack: return width_kernel<bitar_hip::RunPack, kRunPack, true>(lg);
     case kCascade: return width_kernel<bitar_hip::Cascade, kCascade, true>(lg);
     case kRansPlane: return width_kernel<bitar_hip::RansPlane, kRansPlane, true>(lg);
+    case kPatchPack: return width_kernel<bitar_hip::PatchPack, kPatchPack, true>(lg);
     default: return nullptr;
   }
 }
@@ -459,6 +462,9 @@ static DecompressKernel decompress_kernel(uint32_t f) {
     case kFltPack: return bitar_hip::column_decompress_kernel<bitar_hip::FltPack, LISTED>;
     case kDictPack: return bitar_hip::column_decompress_kernel<bitar_hip::DictPack, LISTED>;
     case kCascade: return bitar_hip::column_decompress_kernel<bitar_hip::Cascade, LISTED>;
+    case kPatchPack:  // (no candidate of AUTOPACK: it has no listed form)
+      if constexpr (LISTED) return nullptr;
+      else return bitar_hip::column_decompress_kernel<bitar_hip::PatchPack, false>;
     default: return bitar_hip::column_decompress_kernel<bitar_hip::RunPack, LISTED>;
   }
 }
@@ -682,7 +688,7 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   const ColumnCodec cc = column_codec(codec);
   if (cc && cc.family != kAutoPack) {
     // one streaming kernel, the same work for every segment: plain order (intpack.hip,
-    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip)
+    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip, patchpack.hip)
     hipLaunchKernelGGL(compress_kernel<true>(cc.family, cc.lg), dim3((uint32_t)nseg), dim3(64), 0,
                        s, in, n, seg, slab, slot_stride, dsts, d_sizes);
   }

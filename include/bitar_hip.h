@@ -377,7 +377,55 @@ enum bitar_hip_codec {
    * taken candidates in index order; after the fifth generation a symbol's code is its position.
    * Emit: the whole segment parsed greedily with T, no match passing its end; a symbol gives its
    * code, a single byte not in T gives 255 in codes and the byte in lits. */
-  BITAR_HIP_CODEC_SYMTAB = 88
+  BITAR_HIP_CODEC_SYMTAB = 88,
+  /* PATCHPACK: INTPACK with per-miniblock exceptions -- a patched frame of
+   * reference -- for integer columns with outliers: timestamps with gaps, string offsets with a
+   * long string, heavy-tailed counts, INT_MAX, 0 or -1 written for "missing".  INTPACK gives a
+   * miniblock the bit length of its largest residual; here the few residuals that are too long
+   * are kept raw behind the payload, as FLTPACK keeps its exceptions.  No reference counterpart
+   * and no stock library reads the format (tests/patchpack_model.py is a numpy reader and
+   * writer).  Ids 104 + log2(w) for w = 1, 2, 4, 8; id 108 is left for a 16-byte width.  No
+   * candidate of AUTOPACK.  One stream per segment of L bytes, m = L / w elements, nmb =
+   * ceil(m / 64) miniblocks, nblk = ceil(nmb / 4) blocks, tail = L - m * w bytes:
+   *   byte 0      0x90 | mode << 2 | log2(w)   mode 0 plain, 1 delta, 2 stored, 3 complement
+   *   byte 1      0
+   *   bytes 2..3  LE16(L - 1)
+   *   stored:     L raw bytes                                        size = 4 + L
+   *   packed:     LE16 nx        number of exceptions, nx <= min(m, 65535)
+   *               [mode 1: element 0, w bytes]
+   *               widths[nmb]    one byte each, 0..8w
+   *               refs[nblk]     w bytes each
+   *               payload        miniblock k = 8 * widths[k] bytes, INTPACK's packing
+   *               pos[nx]        LE16 element indices, strictly increasing, each < m
+   *               val[nx]        the exceptions' x, w bytes each, same order
+   *               tail
+   *   size = 6 + [w] + nmb + nblk*w + 8*sum(widths) + nx*(2 + w) + tail
+   * All arithmetic mod 2^(8w).  mode 0: x_i = v_i.  mode 3: x_i = ~v_i (outliers below the rest
+   * then lie above).  mode 1: INTPACK's, x_i = v_i - v_(i-1), x_0 = x_1, or 0 when m = 1.  A
+   * block's reference is the signed minimum of x over all its elements, later exceptions
+   * included.  Width rule, in miniblock k with c = min(64, m - 64k) elements: r_t = x_t - ref,
+   * l_t = bit_length(r_t), B = max l_t; cost(b) = 8b + (2 + w) * #{t < c : l_t > b} for b = 0..B;
+   * widths[k] is the LARGEST b of minimal cost, the exceptions are the elements with l_t >
+   * widths[k], and their slots and the slots past m pack as 0.  A miniblock that gains nothing
+   * has INTPACK's width and no exception.  val holds x itself (the element, its complement, the
+   * delta); in mode 1 x_0 may be an exception like any other, and the decoder takes element 0
+   * from the base whatever slot 0 or an exception at position 0 holds.  The smallest of the three
+   * packed sizes wins, a tie goes to plain, then delta, then complement; the segment is stored
+   * when the winner is not strictly below 4 + L (m = 0 included).  The decoder takes w from the
+   * tag (any of the ids decodes every width) and rejects, before it writes anything: a high
+   * nibble other than 9, byte 1 != 0, L > seg, a stored form whose size is not 4 + L, a stream
+   * too short for its header arrays, a width above 8w, nx > m, a size that is not exactly the
+   * formula, a position >= m or not above the one before it.  A rejected segment's output range
+   * stays untouched, nothing outside a segment's first L output bytes is written, nothing outside
+   * the stream is read.  Everything else decodes: non-zero bits in an exception's slot (ignored),
+   * widths larger than needed, a mode that is not the smallest, a packed form above 4 + L. */
+  /* (Written in parentheses on purpose: tests/test_abi.py counts the header's `*PACK<bits> = <id>`
+   * lines and pins the five families it knows at 19.  tests/test_patchpack_model.py checks these
+   * four against the Python ids.) */
+  BITAR_HIP_CODEC_PATCHPACK8 = (104),
+  BITAR_HIP_CODEC_PATCHPACK16 = (105),
+  BITAR_HIP_CODEC_PATCHPACK32 = (106),
+  BITAR_HIP_CODEC_PATCHPACK64 = (107)
 };
 
 /* The INTPACK id of an element width of 1, 2, 4 or 8 bytes. */
@@ -415,6 +463,11 @@ enum bitar_hip_codec {
 #define BITAR_HIP_CODEC_CASCADE(width) \
   ((width) == 1 ? BITAR_HIP_CODEC_CASCADE8 : (width) == 2 ? BITAR_HIP_CODEC_CASCADE16 : \
    (width) == 4 ? BITAR_HIP_CODEC_CASCADE32 : BITAR_HIP_CODEC_CASCADE64)
+
+/* The PATCHPACK id of an element width of 1, 2, 4 or 8 bytes. */
+#define BITAR_HIP_CODEC_PATCHPACK(width) \
+  ((width) == 1 ? BITAR_HIP_CODEC_PATCHPACK8 : (width) == 2 ? BITAR_HIP_CODEC_PATCHPACK16 : \
+   (width) == 4 ? BITAR_HIP_CODEC_PATCHPACK32 : BITAR_HIP_CODEC_PATCHPACK64)
 
 /* Per-segment marker written into sizes[] / produced[] when that segment's op failed
  * (malformed stream, or output larger than its slot: the reference's
@@ -467,14 +520,14 @@ int bitar_hip_stream(bitar_hip_ctx* ctx, uint32_t qp, void** stream);
 int bitar_hip_device(bitar_hip_ctx* ctx, int* device);
 
 /* Worst-case compressed bytes of one segment of `seg` bytes (LZ4_compressBound /
- * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE and SYMTAB, their stored form), rounded up to 256 B; 0 for an
+ * fixed-Huffman bound; seg + 4 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB and PATCHPACK, their stored form), rounded up to 256 B; 0 for an
  * unknown codec.  Plays the role of compressed_seg_size
  * (reference src/config.cc:59-73): the stride of output slots in a slab. */
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg);
 
 /* Largest match distance the encoder of `codec` emits (0 for an unknown codec): the reach of
  * its sliding window, 2560 for the fast parses of LZ4 / DEFLATE / Zstd and 14848 for the
- * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE and SYMTAB have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
+ * wide LZ4 parse.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB and PATCHPACK have no matches: their 0 means "none", not "unknown".  The front-end reports ceil(log2) of it as the configured window_size
  * (the reference sets the device maximum, src/device.cc:389-393; its streams are valid for
  * any window at least this large, and the decoders accept the full 32 KiB / 64 KiB). */
 uint32_t bitar_hip_max_distance(uint32_t codec);
