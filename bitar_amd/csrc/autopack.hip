@@ -10,6 +10,7 @@
 // that is not candidate 0 over the slot.  Decompress sorts the segments by the high nibble of
 // byte 0 (autopack_route_kernel) and runs each format's decoder over its own segments
 // (*_decompress_listed_kernel in the four codecs' files).
+#include "kernels.hip.h"
 #include "../../include/bitar_hip.h"
 #include "wave.hip.h"
 

@@ -8,8 +8,10 @@
 //   F::EncShared<W>, F::DecShared       the LDS of its encoder (element width W) and decoder
 //   F::compress_segment<W, STORE>(src, L, dst, size_out, sh)
 //   F::decode_stream(src, csize, tag, byte1, L, seg, dst, sh) -> bool
-// runtime.hip names the kernels' instantiations through the declarations alone
-// (BITAR_COLUMN_DECLARATIONS_ONLY): the traits types stay incomplete there.
+// runtime.hip includes this header with BITAR_COLUMN_DECLARATIONS_ONLY: it sees the two kernel
+// templates' declarations below (the other kernels' are in kernels.hip.h) and the traits types'
+// names, which stay incomplete there, and its column table (kColumn, compress_kernel<>,
+// decompress_kernel<>) names the instantiations the formats' files define.
 #pragma once
 
 #include "../../include/bitar_hip.h"
@@ -23,6 +25,10 @@ struct DictPack;
 struct RunPack;
 struct Cascade;
 struct PatchPack;
+struct Rans;       // (rans.hip)
+struct RansPlane;  // (ransplane.hip; a decoder per element width)
+template <uint32_t W> struct RansPlaneDecoder;
+struct SymTab;     // (symtab.hip)
 
 // Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
 // or dsts[i]); sizes[i] = the stream's size (at most 4 + the segment's length: never a failure).

@@ -422,6 +422,5 @@ BITAR_COLUMN_COMPRESS(Cascade, 2, true);
 BITAR_COLUMN_COMPRESS(Cascade, 4, true);
 BITAR_COLUMN_COMPRESS(Cascade, 8, true);
 BITAR_COLUMN_DECOMPRESS(Cascade, false);
-BITAR_COLUMN_DECOMPRESS(Cascade, true);
 
 }  // namespace bitar_hip

@@ -9,6 +9,7 @@
 // its chunk (CRC32 with a 1 KiB LDS table; Adler32 as plain and position-weighted sums), and
 // the chunks are combined in GF(2) (crc(A||B) = x^(8|B|) * crc(A) + crc(B) mod P, zlib's
 // crc32_combine) and modulo 65521.
+#include "kernels.hip.h"
 #include "crc32.hip.h"
 #include "wave.hip.h"
 

@@ -16,6 +16,7 @@
 //        rare long runs fall back to a per-sequence path (long literal runs go HBM->HBM);
 //   DEFLATE: every position lane contributes its literal code or its match symbol; codes
 //        are placed by a prefix sum of bit lengths and OR-ed into an LDS bit ring.
+#include "kernels.hip.h"
 #include "window_parse.hip.h"
 
 namespace bitar_hip {

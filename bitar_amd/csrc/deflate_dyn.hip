@@ -19,6 +19,7 @@
 //                             records and the input bytes.
 // The parse (the expensive part, ~250 instructions per window) runs once; the emit pass is
 // a streaming read of records + input and write of the stream.
+#include "kernels.hip.h"
 #include "huffman.hip.h"
 #include "window_parse.hip.h"
 

@@ -27,6 +27,7 @@
 // segment, the head and tail of a stored body, a stored header bit) is merged with atomicOr
 // into the output the caller's memset zeroed.  So a dword is either owned by one wave or
 // touched by atomics alone, however many segments share it.
+#include "kernels.hip.h"
 #include "crc32.hip.h"
 #include "wave.hip.h"
 

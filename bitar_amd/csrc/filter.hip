@@ -28,6 +28,7 @@
 // A block belongs to the tile that holds its first byte, so the apply loads BS row positions
 // more than a tile (re-read from L2), and the invert loads the blocks at a tile's edges twice.
 // Workgroups never wait for one another.
+#include "kernels.hip.h"
 #include "wave.hip.h"
 
 // Tile bytes, measured: the apply is 11-28 % faster with 8 KiB tiles (18 KB of

@@ -10,6 +10,7 @@
 // from LDS fast tables (10-bit literal/length, 9-bit distance, canonical fallback for longer
 // codes), literals gather in a lane vector and land in the history ring 64 at a time, and
 // matches / stored blocks reuse the window + ring machinery of stream_ring.hip.h.
+#include "kernels.hip.h"
 #include "stream_ring.hip.h"
 
 // Fast-table sizes, namespace and kernel name: inflate_fixed.hip builds this file a second

@@ -19,6 +19,7 @@
 // Stored blocks are copied by the whole wave, one lane's block at a time (coalesced).
 // Bytes of a segment's output slot past its produced size are unspecified (match
 // wildcopies may write up to 32 bytes past the current output position, inside the slot).
+#include "kernels.hip.h"
 #include "lane_copy.hip.h"
 
 namespace bitar_hip {

@@ -8,6 +8,7 @@
 // Acceptance: the block format of bo_lz4_decompress_block (oracle/bitar_oracle.c) applied to
 // the concatenated output -- a match offset must be 1..(bytes produced so far), every block
 // ends right after a literal run.
+#include "kernels.hip.h"
 #include "stream_ring.hip.h"
 
 namespace bitar_hip {

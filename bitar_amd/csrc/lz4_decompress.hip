@@ -27,6 +27,7 @@
 //               blocks are flushed to HBM with dwordx4 stores, 1 KiB per wave instruction.
 //   Matches reaching further back than the ring read HBM, behind a lazily placed fence.
 //   Literal runs >= kLongLit bypass the ring and stream HBM -> HBM (wave_copy_global).
+#include "kernels.hip.h"
 #include "stream_ring.hip.h"
 
 #include <type_traits>

@@ -12,134 +12,17 @@
 #include <list>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bitar_hip.h"
 #include "../../include/bitar_hip_snappy.h"
 #define BITAR_COLUMN_DECLARATIONS_ONLY  // (the kernels are defined in the formats' files)
 #include "autopack.hip.h"
+#include "kernels.hip.h"
 #include "order.hip.h"
 #include "zstd_hand.hip.h"
 #include "zstd_layout.hip.h"
-
-namespace bitar_hip {
-struct Rans;  // (rans.hip: the column kernels with the rANS format's traits)
-struct RansPlane;  // (ransplane.hip: the same per byte plane; a decoder per element width)
-template <uint32_t W> struct RansPlaneDecoder;
-struct SymTab;  // (symtab.hip: the same with the symbol-table format's traits)
-template <uint32_t RING, uint32_t HLOG>
-__global__ void lz4_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                    uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
-template <bool FARK>
-__global__ void lz4_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                      const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                      uint32_t*, unsigned long long*, const uint32_t*);
-__global__ void snappy_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                       uint8_t* const*, uint32_t*, const uint32_t*);
-template <bool JOINED>
-__global__ void snappy_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                         const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                         uint32_t*, const uint32_t*);
-__global__ void snappy_joined_key_kernel(const uint64_t*, uint32_t, uint32_t*);
-__global__ void snappy_join_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint32_t*);
-__global__ void snappy_join_kernel(const uint8_t*, uint64_t, const uint32_t*, uint64_t*, uint32_t,
-                                   uint64_t, uint8_t*, uint64_t, uint64_t*, uint32_t*);
-__global__ void snappy_scan_init_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t*, uint32_t*,
-                                        uint4*, uint32_t*, uint32_t);
-__global__ void snappy_scan_walk_kernel(const uint8_t*, uint32_t, uint32_t, const uint32_t*, uint4*,
-                                        uint2*, const uint2*);
-__global__ void snappy_scan_resolve_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t, uint32_t,
-                                           uint32_t*, uint4*, const uint2*, uint4*, uint2*,
-                                           uint64_t*, uint32_t*);
-__global__ void snappy_scan_serial_kernel(const uint8_t*, uint32_t, uint64_t, uint64_t, uint32_t,
-                                          uint32_t*, const uint4*, uint64_t*, uint32_t*, uint32_t);
-__global__ void snappy_scan_finish_kernel(const uint8_t*, uint32_t, uint64_t, uint32_t,
-                                          const uint32_t*, const uint4*, const uint4*, uint64_t*,
-                                          uint32_t*);
-__global__ void seg_cost_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
-__global__ void order_hist_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                                  uint32_t*);
-__global__ void order_scatter_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                                     uint32_t, const uint32_t*, uint32_t*);
-__global__ void deflate_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                        uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
-__global__ void deflate_compress_bits_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,
-                                             uint64_t, uint8_t* const*, uint32_t*, uint32_t*,
-                                             const uint32_t*, uint32_t*);
-__global__ void inflate_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                               const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                               uint32_t*, uint32_t, unsigned long long*, const uint32_t*);
-__global__ void inflate_fixed_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                               const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                               uint32_t*, uint32_t, unsigned long long*, const uint32_t*);
-template <uint32_t L>
-__global__ void inflate_lanes_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                     const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*);
-__global__ void zstd_parse_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t, uint2*, const uint32_t*);
-__global__ void zstd_entropy_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                    const uint2*, uint8_t*, uint64_t, const uint32_t*);
-__global__ void zstd_walk_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint8_t*, uint64_t,
-                                 const uint32_t*);
-__global__ void walk_key_kernel(const uint2*, uint32_t, uint32_t*);
-__global__ void zstd_emit_kernel(const uint8_t*, uint64_t, uint32_t, const uint8_t*, uint64_t,
-                                 uint8_t*, uint64_t, uint8_t* const*, uint32_t*, const uint8_t*,
-                                 uint64_t, const uint32_t*);
-__global__ void zstd_decompress_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                       const uint32_t*, uint32_t, uint32_t, uint8_t*,
-                                       uint32_t*, uint32_t*, uint32_t, uint8_t*,
-                                       unsigned long long*, const uint32_t*, uint32_t);
-template <uint32_t S, uint32_t B>
-__global__ void zstd_hlit_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                 const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                 const uint8_t*, uint32_t*, const uint32_t*);
-__global__ void hand_key_kernel(const uint32_t*, const uint8_t*, uint32_t, uint32_t, uint32_t*);
-template <uint32_t L>
-__global__ void zstd_handoff_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                    const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*,
-                                    const uint8_t*, uint32_t*);
-template <uint32_t L, uint32_t B>
-__global__ void zstd_seqdec_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                   const uint32_t*, uint32_t, uint32_t, uint32_t*, uint8_t*,
-                                   uint64_t*, uint32_t, uint32_t*, unsigned long long*, const uint32_t*);
-__global__ void zstd_exec_kernel(const uint8_t* const*, const uint8_t*, uint64_t, uint32_t,
-                                 uint32_t, uint8_t*, uint32_t*, const uint8_t*,
-                                 const uint64_t*, uint32_t, uint32_t*, unsigned long long*, const uint32_t*);
-template <uint32_t L>
-__global__ void zstd_lanes_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                  const uint32_t*, uint32_t, uint32_t, uint8_t*, uint32_t*);
-__global__ void deflate_dyn_parse_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
-                                         uint32_t*, const uint32_t*);
-__global__ void deflate_dyn_emit_kernel(const uint8_t*, uint64_t, uint32_t, const uint8_t*,
-                                        uint64_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*,
-                                        uint32_t*, const uint32_t*, uint32_t*);
-__global__ void join_scan_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint32_t*,
-                                 uint32_t, uint64_t, uint64_t*, uint32_t*);
-__global__ void deflate_join_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint32_t*,
-                                    uint32_t, const uint64_t*, uint32_t*, uint64_t);
-__global__ void deflate_split_kernel(const uint8_t*, uint64_t, const uint64_t*, const uint32_t*,
-                                     uint32_t, uint8_t*, uint64_t, uint32_t*, uint32_t*);
-__global__ void crc32_combine_kernel(const uint64_t*, uint64_t, uint32_t, uint32_t, uint32_t*);
-__global__ void checksum_kernel(uint32_t, const uint8_t*, uint64_t, uint32_t, const uint32_t*,
-                                uint32_t, uint64_t*);
-template <uint32_t W, bool BITS, bool INV>
-__global__ void filter_kernel(const uint8_t*, uint64_t, uint32_t, const uint32_t*, uint32_t,
-                              uint8_t*);
-__global__ void autopack_select_kernel(const uint8_t*, uint64_t, const uint32_t*, uint32_t, uint32_t,
-                                       uint32_t, uint8_t*, uint64_t, uint8_t* const*, uint32_t*);
-__global__ void autopack_route_kernel(const uint8_t* const*, const uint8_t*, uint64_t,
-                                      const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*,
-                                      uint32_t*);
-__global__ void scan_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint64_t*, uint32_t*);
-__global__ void pack_kernel(const uint8_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t,
-                            uint8_t*);
-__global__ void fill_kernel(int, uint64_t, uint64_t, uint8_t*, uint64_t);
-__global__ void lz4_chain_kernel(const uint8_t*, uint32_t, const uint32_t*, uint32_t, uint8_t*,
-                                 uint32_t, uint32_t*, uint32_t*);
-__global__ void copy_batch_kernel(const uint8_t* const*, uint8_t* const*, const uint32_t*, uint32_t);
-__global__ void lz4f_sizes_kernel(const uint32_t*, uint32_t, uint64_t, uint32_t, uint32_t*);
-__global__ void lz4f_pack_kernel(const uint8_t*, uint64_t, uint32_t, const uint8_t*, uint64_t,
-                                 const uint32_t*, const uint64_t*, uint32_t, uint8_t*);
-}  // namespace bitar_hip
 
 // Error words: one sticky uint32 per stream (bit0 decode error, bit1 slot overflow, bit2 a
 // failed segment handed to pack).  Word 0 serves the NULL stream, word q+1 queue pair q, and
@@ -155,7 +38,7 @@ struct bitar_hip_ctx {
   unsigned long long* d_stats = nullptr;  // BITAR_HIP_PATH_COUNT path counters
   // decoder options (bitar_hip_decoder_options), per context
   std::atomic<uint32_t> inflate_lanes{4}, zstd_lanes{16}, zstd_seq{1}, count_paths{0};
-  std::atomic<uint32_t> zstd_fork{1};  // Zstd literals beside phase A (decompress_impl)
+  std::atomic<uint32_t> zstd_fork{1};  // Zstd literals beside phase A (decompress_zstd)
   std::atomic<uint32_t> cost_order{1};  // LZ4: dispatch the estimated most expensive segments first
   std::mutex mu;              // guards `words` and `order_scratch`
   std::vector<std::pair<hipStream_t, uint32_t>> words;  // stream -> error word index
@@ -378,7 +261,10 @@ extern "C++" {
 // The column codecs: a family's ids are base + log2(element width) for the widths it offers
 // (`widths`: those widths ORed together, so bit lg stands for 1 << lg bytes), and its streams
 // carry `nibble` in the high half of byte 0
-// (AUTOPACK has no format of its own).  Two orders here are load-bearing:
+// (AUTOPACK has no format of its own).  CASCADE, RANSPLANE, PATCHPACK, RANS and SYMTAB are no
+// candidates of AUTOPACK: they have no store-less encoder and no listed decoder, and they come
+// after the families that do.  RANS and SYMTAB are byte codecs run by the column kernels: one id
+// each, width 1.  Two orders here are load-bearing:
 //   Candidate order (AUTOPACK compress): RUNPACK first, into the caller's slot; then INTPACK,
 //     DICTPACK, FLTPACK into scratch slabs k = 0, 1, 2.  autopack_select_kernel breaks ties
 //     towards the earlier candidate.
@@ -386,8 +272,8 @@ extern "C++" {
 //     nibble 4 + f -- INTPACK, FLTPACK, DICTPACK, RUNPACK -- which is what autopack_route_kernel
 //     writes.
 enum ColumnFamily : int {
-  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kPatchPack,
-  kColumnFamilies
+  kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kPatchPack, kRans,
+  kSymTab, kColumnFamilies
 };
 struct ColumnRow {
   uint32_t base, nibble, widths;
@@ -401,6 +287,8 @@ constexpr ColumnRow kColumn[kColumnFamilies] = {
     {BITAR_HIP_CODEC_CASCADE8, 8, 1 | 2 | 4 | 8},            // CASCADE (no candidate of AUTOPACK)
     {BITAR_HIP_CODEC_RANSPLANE16 - 1, 0xB, 2 | 4 | 8},       // RANSPLANE (likewise)
     {BITAR_HIP_CODEC_PATCHPACK8, 9, 1 | 2 | 4 | 8},          // PATCHPACK (likewise)
+    {BITAR_HIP_CODEC_RANS, 0xA, 1},                          // RANS (likewise; bytes)
+    {BITAR_HIP_CODEC_SYMTAB, 0xC, 1},                        // SYMTAB (likewise; bytes)
 };
 constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
 constexpr uint32_t kListedDecoders = 4;
@@ -452,30 +340,75 @@ static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
     case kCascade: return width_kernel<bitar_hip::Cascade, kCascade, true>(lg);
     case kRansPlane: return width_kernel<bitar_hip::RansPlane, kRansPlane, true>(lg);
     case kPatchPack: return width_kernel<bitar_hip::PatchPack, kPatchPack, true>(lg);
+    case kRans: return width_kernel<bitar_hip::Rans, kRans, true>(lg);
+    case kSymTab: return width_kernel<bitar_hip::SymTab, kSymTab, true>(lg);
     default: return nullptr;
   }
 }
+// The decoder of a family (not AUTOPACK).  A stream's tag carries its width, so the families
+// ignore lg, but for RANSPLANE: one decoder per element width (its LDS is the width's), and an id
+// decodes its own width alone.  LISTED: AUTOPACK's decoder of one of its candidates' formats; the
+// other families have no listed form.
 template <bool LISTED>
-static DecompressKernel decompress_kernel(uint32_t f) {
+static DecompressKernel decompress_kernel(uint32_t f, uint32_t lg) {
+  using namespace bitar_hip;
   switch (f) {
-    case kIntPack: return bitar_hip::column_decompress_kernel<bitar_hip::IntPack, LISTED>;
-    case kFltPack: return bitar_hip::column_decompress_kernel<bitar_hip::FltPack, LISTED>;
-    case kDictPack: return bitar_hip::column_decompress_kernel<bitar_hip::DictPack, LISTED>;
-    case kCascade: return bitar_hip::column_decompress_kernel<bitar_hip::Cascade, LISTED>;
-    case kPatchPack:  // (no candidate of AUTOPACK: it has no listed form)
-      if constexpr (LISTED) return nullptr;
-      else return bitar_hip::column_decompress_kernel<bitar_hip::PatchPack, false>;
-    default: return bitar_hip::column_decompress_kernel<bitar_hip::RunPack, LISTED>;
+    case kIntPack: return column_decompress_kernel<IntPack, LISTED>;
+    case kFltPack: return column_decompress_kernel<FltPack, LISTED>;
+    case kDictPack: return column_decompress_kernel<DictPack, LISTED>;
+    case kRunPack: return column_decompress_kernel<RunPack, LISTED>;
   }
+  if constexpr (!LISTED) {
+    switch (f) {
+      case kCascade: return column_decompress_kernel<Cascade, false>;
+      case kPatchPack: return column_decompress_kernel<PatchPack, false>;
+      case kRans: return column_decompress_kernel<Rans, false>;
+      case kSymTab: return column_decompress_kernel<SymTab, false>;
+      case kRansPlane:
+        switch (lg) {
+          case 1: return column_decompress_kernel<RansPlaneDecoder<2>, false>;
+          case 2: return column_decompress_kernel<RansPlaneDecoder<4>, false>;
+          default: return column_decompress_kernel<RansPlaneDecoder<8>, false>;
+        }
+    }
+  }
+  return nullptr;
 }
-// RANSPLANE's decoders: one per element width (its LDS is the width's), and an id decodes its
-// own width alone
-static DecompressKernel ransplane_decompress_kernel(uint32_t lg) {
-  switch (lg) {
-    case 1: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<2>, false>;
-    case 2: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<4>, false>;
-    default: return bitar_hip::column_decompress_kernel<bitar_hip::RansPlaneDecoder<8>, false>;
-  }
+
+// What the entry points know about an id: the format it decodes as (its own, or the one two
+// parses share; 0: no such codec), the worst-case size of a segment's stream, the largest match
+// distance its encoder emits, and its column family if it has one.  kByte has a row per byte
+// codec; find_codec() looks there and in kColumn, and nothing else lists the ids that exist.
+// The window-scan parse verifies candidates in its LDS input ring, which runs up to 1536 B
+// ahead of the scan: a 4 KiB ring (window_parse.hip.h kMaxDist) for the fast parses of LZ4,
+// DEFLATE and Zstd, a 16 KiB ring for the wide LZ4 parse (compress.hip, lz4_wide).  A column
+// codec's max distance of 0 is "none", it has no matches at all; an unknown id's is "unknown".
+struct Codec {
+  uint32_t id, format;
+  uint64_t (*bound)(uint64_t seg);
+  uint32_t max_distance;
+  ColumnCodec column = {kColumnFamilies, 0};
+  explicit operator bool() const { return format != 0; }
+};
+constexpr uint64_t column_bound(uint64_t n) { return n + 4u; }  // the stored form: header + the segment
+constexpr uint64_t lz4_bound(uint64_t n) { return n + n / 255u + 16u; }  // LZ4_compressBound
+constexpr uint64_t snappy_bound(uint64_t n) { return n + 6u; }  // the stored form: varint + tag + segment
+constexpr uint64_t deflate_bound(uint64_t n) { return (n * 9 + 7) / 8 + 16u; }  // fixed Huffman, 9 bits/literal
+constexpr uint64_t zstd_bound(uint64_t n) { return n + 7u + 3u + 8u + 512u; }  // oracle bo_zstd_bound: one block, raw if larger
+constexpr uint32_t kFastReach = 4096u - 1536u, kWideReach = 16384u - 1536u;
+constexpr Codec kByte[] = {
+    {BITAR_HIP_CODEC_LZ4, BITAR_HIP_CODEC_LZ4, lz4_bound, kFastReach},
+    {BITAR_HIP_CODEC_LZ4_WIDE, BITAR_HIP_CODEC_LZ4, lz4_bound, kWideReach},  // same format
+    {BITAR_HIP_CODEC_SNAPPY, BITAR_HIP_CODEC_SNAPPY, snappy_bound, kFastReach},  // (the LZ4 codec's parse)
+    {BITAR_HIP_CODEC_DEFLATE, BITAR_HIP_CODEC_DEFLATE, deflate_bound, kFastReach},
+    {BITAR_HIP_CODEC_DEFLATE_DYNAMIC, BITAR_HIP_CODEC_DEFLATE, deflate_bound, kFastReach},  // same format
+    {BITAR_HIP_CODEC_ZSTD, BITAR_HIP_CODEC_ZSTD, zstd_bound, kFastReach},
+};
+static Codec find_codec(uint32_t id) {
+  for (const Codec& r : kByte)
+    if (r.id == id) return r;
+  if (const ColumnCodec cc = column_codec(id)) return {id, id, column_bound, 0, cc};
+  return {};
 }
 }  // extern "C++"
 
@@ -495,39 +428,11 @@ static bool autopack_storeless() {
 }
 
 uint64_t bitar_hip_slot_size(uint32_t codec, uint32_t seg) {
-  uint64_t bound;
-  if (column_codec(codec))
-    bound = (uint64_t)seg + 4u;                         // the stored form: header + the segment
-  else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE)
-    bound = (uint64_t)seg + seg / 255u + 16u;           // LZ4_compressBound
-  else if (codec == BITAR_HIP_CODEC_SNAPPY)
-    bound = (uint64_t)seg + 6u;                         // the stored form: varint + tag + segment
-  else if (codec == BITAR_HIP_CODEC_RANS || codec == BITAR_HIP_CODEC_SYMTAB)
-    bound = (uint64_t)seg + 4u;                         // the stored form, as the column codecs'
-  else if (codec == BITAR_HIP_CODEC_DEFLATE || codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC)
-    bound = ((uint64_t)seg * 9 + 7) / 8 + 16u;          // fixed Huffman, 9 bits/literal
-  else if (codec == BITAR_HIP_CODEC_ZSTD)  // oracle bo_zstd_bound: one block, raw if larger
-    bound = (uint64_t)seg + 7u + 3u + 8u + 512u;
-  else
-    return 0;
-  return (bound + 255u) & ~(uint64_t)255u;
+  const Codec c = find_codec(codec);
+  return c ? (c.bound(seg) + 255u) & ~(uint64_t)255u : 0;
 }
 
-uint32_t bitar_hip_max_distance(uint32_t codec) {
-  // the window-scan parse verifies candidates in its LDS input ring, which runs up to 1536 B
-  // ahead of the scan: a 4 KiB ring (window_parse.hip.h kMaxDist) for the fast parses of LZ4,
-  // DEFLATE and Zstd, a 16 KiB ring for the wide LZ4 parse (compress.hip, lz4_wide)
-  switch (codec) {
-    case BITAR_HIP_CODEC_LZ4:
-    case BITAR_HIP_CODEC_SNAPPY:  // (the LZ4 codec's parse)
-    case BITAR_HIP_CODEC_DEFLATE:
-    case BITAR_HIP_CODEC_DEFLATE_DYNAMIC:
-    case BITAR_HIP_CODEC_ZSTD: return 4096u - 1536u;
-    case BITAR_HIP_CODEC_LZ4_WIDE: return 16384u - 1536u;
-    // a column codec: "none", it has no matches at all; any other id: "unknown", no such codec
-    default: return 0;
-  }
-}
+uint32_t bitar_hip_max_distance(uint32_t codec) { return find_codec(codec).max_distance; }
 
 int bitar_hip_alloc(bitar_hip_ctx* ctx, uint64_t bytes, void** ptr) {
   if (int r = enter(ctx)) return r;
@@ -571,6 +476,9 @@ int bitar_hip_memcpy(bitar_hip_ctx* ctx, void* dst, const void* src, uint64_t by
 // regions of columns / text / random data): see DESIGN.md 4.1.
 extern "C++" {
 constexpr uint32_t kOrderMinSegs = 2048;
+// An order is an optimisation only: make() cannot fail, and where its scratch cannot be
+// allocated (or the call is too small, or ordering is off) the call runs in plain order
+// (order == nullptr).
 struct SegOrder {
   bitar_hip_ctx::OrderScratch* e = nullptr;
   std::unique_lock<std::mutex> held;
@@ -583,9 +491,9 @@ struct SegOrder {
   // uses slots 0 and 1).  The scratch is allocated once per stream and grown on demand, so
   // steady-state calls queue no allocation.
   template <class F>
-  int make(bitar_hip_ctx* ctx, hipStream_t s, uint32_t nseg, const uint32_t* csizes, F key,
-           uint32_t seg = 0, int slot = 0) {
-    if (!ctx->cost_order.load(std::memory_order_relaxed) || nseg < kOrderMinSegs) return 0;
+  void make(bitar_hip_ctx* ctx, hipStream_t s, uint32_t nseg, const uint32_t* csizes, F key,
+            uint32_t seg = 0, int slot = 0) {
+    if (!ctx->cost_order.load(std::memory_order_relaxed) || nseg < kOrderMinSegs) return;
     const uint32_t tile = bitar_hip::order_tile(nseg);
     const uint32_t ntiles = (nseg + tile - 1) / tile;
     const uint64_t need = 8ull * nseg + 4ull * bitar_hip::kOrderBins * ntiles + 64;
@@ -598,7 +506,7 @@ struct SegOrder {
       if (hipMallocAsync(&transient, need, s) != hipSuccess) {
         (void)hipGetLastError();
         transient = nullptr;
-        return 0;  // (an optimisation only: the call runs in plain order)
+        return;
       }
       tstream = s;
     } else {
@@ -610,7 +518,6 @@ struct SegOrder {
       }
       held = std::unique_lock<std::mutex>(e->m);
       if (e->cap < need) {
-        // (an optimisation only: without scratch the call runs in plain order)
         if (e->p) (void)hipFreeAsync(e->p, s);
         e->p = nullptr;
         e->cap = 0;
@@ -619,7 +526,7 @@ struct SegOrder {
           (void)hipGetLastError();
           e->p = nullptr;
           held.unlock();
-          return 0;
+          return;
         }
         e->cap = cap;
       }
@@ -633,14 +540,12 @@ struct SegOrder {
                        seg, nseg, tile, hist);
     hipLaunchKernelGGL(bitar_hip::order_scatter_kernel, dim3(ntiles), dim3(64), 0, s, keys,
                        csizes, seg, nseg, tile, ntiles, hist, order);
-    return 0;
   }
   // after the last launch that reads the order has been queued
-  int release() {
+  void release() {
     if (held.owns_lock()) held.unlock();
     if (transient) (void)hipFreeAsync(transient, tstream);
     transient = nullptr;
-    return 0;
   }
   ~SegOrder() { release(); }
 };
@@ -652,17 +557,207 @@ static void free_order_scratch(bitar_hip_ctx* ctx) {
     if (x.p) (void)hipFree(x.p);
   ctx->order_scratch.clear();
 }
-}  // extern "C++"
+
+// ---- compress: one function per format, dispatched by compress_impl ------------------------
+// What every format's function takes (validated by compress_impl): segment i is min(seg, n -
+// i * seg) bytes at in + i * seg, its slot slab + i * stride or dsts[i].  chunk(): the same for
+// the segments [c0, c0 + most) of the call -- every per-segment pointer moved up by c0.
+struct CompressArgs {
+  const uint8_t* in;
+  uint64_t n;
+  uint32_t seg, nseg;  // nseg = ceil(n / seg)
+  uint8_t* slab;
+  uint64_t stride;
+  uint8_t* const* dsts;
+  uint32_t *sizes, *bits;  // bits: DEFLATE's bit lengths (bitar_hip_compress_bits), else null
+  CompressArgs chunk(uint64_t c0, uint64_t most) const {
+    const uint64_t cn = nseg - c0 < most ? nseg - c0 : most;
+    const uint64_t cb = c0 * seg, nb = n - cb < cn * seg ? n - cb : cn * seg;
+    return {in + cb, nb, seg, (uint32_t)cn, slab ? slab + c0 * stride : nullptr, stride,
+            dsts ? dsts + c0 : nullptr, sizes + c0, bits ? bits + c0 : nullptr};
+  }
+};
+
+// cost-ordered dispatch of the segments of a call or chunk: key = distinct byte values in a
+// 128-byte sample of each segment (incompressible segments, which the parses skip through and
+// whose stored form is a copy, show the most)
+static void cost_order(bitar_hip_ctx* ctx, hipStream_t s, SegOrder& o, const CompressArgs& a) {
+  o.make(ctx, s, a.nseg, nullptr, [&](uint32_t* keys) {
+    hipLaunchKernelGGL(bitar_hip::seg_cost_kernel, dim3((a.nseg + 15) / 16), dim3(64), 0, s, a.in,
+                       a.n, a.seg, a.nseg, keys);
+  });
+}
+
+// A family's codec: one streaming kernel, the same work for every segment: plain order
+// (intpack.hip, fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip,
+// patchpack.hip, and the byte codecs rans.hip and symtab.hip: one segment's histogram or table,
+// and its coder, in one wave).  A segment never fails (the stored form fits every slot).
+// AUTOPACK: the smallest of the candidates' streams per segment (autopack.hip): RUNPACK straight
+// into the caller's slots, every later candidate that offers the width (kCandidates, kColumn)
+// into a stream-ordered scratch slab of its own with its own sizes (store-less: a segment a
+// later candidate would store gets its size only, and the select kernel never takes it), then
+// the select kernel.  Chunks of <= kAutoChunkSegs segments over one allocation.
+static int compress_column(hipStream_t s, ColumnCodec cc, const CompressArgs& a) {
+  const uint32_t lg = cc.lg;
+  if (cc.family != kAutoPack) {
+    hipLaunchKernelGGL(compress_kernel<true>(cc.family, lg), dim3(a.nseg), dim3(64), 0, s, a.in,
+                       a.n, a.seg, a.slab, a.stride, a.dsts, a.sizes);
+    return 0;
+  }
+  uint32_t extra = 0;  // the candidates after the first
+  for (ColumnFamily f : kCandidates) extra += offers(f, lg) ? 1u : 0u;
+  --extra;
+  const uint64_t scr_stride = bitar_hip_slot_size(kColumn[kAutoPack].base + lg, a.seg);
+  const Chunks ch(a.nseg, kAutoChunkSegs);
+  const bool lean = autopack_storeless();
+  void* scratch = nullptr;
+  HIP_TRY(hipMallocAsync(&scratch, extra * ch.size * (scr_stride + 4u), s), "scratch allocation");
+  auto* scr = static_cast<uint8_t*>(scratch);
+  auto* ssz = reinterpret_cast<uint32_t*>(scr + extra * ch.size * scr_stride);
+  for (uint64_t c0 = 0; c0 < a.nseg; c0 += ch.size) {
+    const CompressArgs c = a.chunk(c0, ch.size);
+    const uint32_t cn = c.nseg;
+    uint32_t k = 0;  // the next scratch candidate
+    for (ColumnFamily f : kCandidates) {
+      if (!offers(f, lg)) continue;
+      if (f == kCandidates[0]) {
+        hipLaunchKernelGGL(compress_kernel<true>(f, lg), dim3(cn), dim3(64), 0, s, c.in, c.n,
+                           c.seg, c.slab, c.stride, c.dsts, c.sizes);
+      } else {
+        const CompressKernel kernel =
+            lean ? compress_kernel<false>(f, lg) : compress_kernel<true>(f, lg);
+        hipLaunchKernelGGL(kernel, dim3(cn), dim3(64), 0, s, c.in, c.n, c.seg,
+                           scr + k * ch.size * scr_stride, scr_stride,
+                           (uint8_t* const*)nullptr, ssz + k * ch.size);
+        ++k;
+      }
+    }
+    hipLaunchKernelGGL(bitar_hip::autopack_select_kernel, dim3((cn + 3) / 4), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(scr), scr_stride,
+                       static_cast<const uint32_t*>(ssz), (uint32_t)ch.size, extra + 1u, cn,
+                       c.slab, c.stride, c.dsts, c.sizes);
+  }
+  const hipError_t le = hipGetLastError();
+  HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+  HIP_TRY(le, "compress launch");
+  return 0;
+}
+
+// LZ4 blocks from the fast parse (4 KiB ring) or the wide one (16 KiB)
+static int compress_lz4(bitar_hip_ctx* ctx, hipStream_t s, bool wide, const CompressArgs& a) {
+  SegOrder ord;
+  cost_order(ctx, s, ord, a);
+  hipLaunchKernelGGL((wide ? bitar_hip::lz4_compress_kernel<16384, 12>
+                           : bitar_hip::lz4_compress_kernel<4096, 10>),
+                     dim3(a.nseg), dim3(64), 0, s, a.in, a.n, a.seg, a.slab, a.stride, a.dsts,
+                     a.sizes, err_word(ctx, s), ord.order);
+  return 0;
+}
+
+// the LZ4 parse with the Snappy emitter (snappy.hip), dispatched as LZ4 is; a segment never
+// fails (the stored form fits every slot), so the kernel takes no error word
+static int compress_snappy(bitar_hip_ctx* ctx, hipStream_t s, const CompressArgs& a) {
+  SegOrder ord;
+  cost_order(ctx, s, ord, a);
+  hipLaunchKernelGGL(bitar_hip::snappy_compress_kernel, dim3(a.nseg), dim3(64), 0, s, a.in, a.n,
+                     a.seg, a.slab, a.stride, a.dsts, a.sizes, ord.order);
+  return 0;
+}
+
+// fixed-Huffman DEFLATE (compress.hip)
+static int compress_deflate(bitar_hip_ctx* ctx, hipStream_t s, const CompressArgs& a) {
+  SegOrder ord;
+  cost_order(ctx, s, ord, a);
+  if (a.bits)  // (a kernel of its own: bitar_hip_compress keeps its code, compress.hip)
+    hipLaunchKernelGGL(bitar_hip::deflate_compress_bits_kernel, dim3(a.nseg), dim3(64), 0, s, a.in,
+                       a.n, a.seg, a.slab, a.stride, a.dsts, a.sizes, err_word(ctx, s), ord.order,
+                       a.bits);
+  else
+    hipLaunchKernelGGL(bitar_hip::deflate_compress_kernel, dim3(a.nseg), dim3(64), 0, s, a.in, a.n,
+                       a.seg, a.slab, a.stride, a.dsts, a.sizes, err_word(ctx, s), ord.order);
+  return 0;
+}
+
+// pass 1 (parse -> records + histograms) and pass 2 (codes + emit) through a stream-ordered
+// scratch per segment (deflate_dyn.hip): 2 KiB plan + the literal stream (<= seg bytes, 16-B
+// aligned) + 8-byte match records (<= seg / 4: matches are >= 4 bytes); the per-window form
+// (BITAR_DYN_BULK 0) needs 2 KiB + 16 KiB of window masks + 4-byte records, within the same
+// stride.  Large calls run in chunks of <= kChunkSegs segments over one scratch allocation, so
+// scratch is bounded whatever the call's size.
+static int compress_deflate_dynamic(bitar_hip_ctx* ctx, hipStream_t s, const CompressArgs& a) {
+  const uint32_t seg = a.seg;
+  const uint64_t scr_old = bitar_hip_slot_size(BITAR_HIP_CODEC_DEFLATE, seg) + 2048u + 16384u;
+  const uint64_t scr_bulk = 2048u + ((seg + 15u) & ~15ull) + 8u * ((uint64_t)seg / 4u + 64u);
+  const uint64_t scr_stride = ((scr_old > scr_bulk ? scr_old : scr_bulk) + 15u) & ~15ull;
+  const Chunks ch(a.nseg);
+  void* scratch = nullptr;
+  HIP_TRY(hipMallocAsync(&scratch, ch.size * scr_stride, s), "scratch allocation");
+  auto* scr = static_cast<uint8_t*>(scratch);
+  for (uint64_t c0 = 0; c0 < a.nseg; c0 += ch.size) {
+    const CompressArgs c = a.chunk(c0, ch.size);
+    const uint32_t cn = c.nseg;
+    SegOrder ord;
+    cost_order(ctx, s, ord, c);
+    hipLaunchKernelGGL(bitar_hip::deflate_dyn_parse_kernel, dim3(cn), dim3(64), 0, s, c.in, c.n,
+                       seg, scr, scr_stride, err_word(ctx, s), ord.order);
+    hipLaunchKernelGGL(bitar_hip::deflate_dyn_emit_kernel, dim3(cn), dim3(64), 0, s, c.in, c.n,
+                       seg, static_cast<const uint8_t*>(scr), scr_stride, c.slab, c.stride, c.dsts,
+                       c.sizes, err_word(ctx, s), ord.order, c.bits);
+  }
+  const hipError_t le = hipGetLastError();
+  HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+  HIP_TRY(le, "compress launch");
+  return 0;
+}
+
+// pass 1 (parse -> literals + sequence records) and pass 2 (entropy coding) through a
+// stream-ordered scratch: per segment the literal area + records (zstd_compress.hip),
+// then {nlit, nseq} per segment
+static int compress_zstd(bitar_hip_ctx* ctx, hipStream_t s, const CompressArgs& a) {
+  const uint32_t seg = a.seg;
+  const uint64_t scr_stride = bitar_hip::zse::scratch_stride(seg);
+  // + the chain-walk scratch (zstd_layout.hip.h: a 5000-byte header with the record, the
+  // literal codes and the FSE tables, then 10 bytes per sequence and 12 per step of <= 64)
+  const uint64_t w_stride = bitar_hip::zse::walk_stride(seg);
+  const Chunks ch(a.nseg);
+  void* scratch = nullptr;
+  HIP_TRY(hipMallocAsync(&scratch, ch.size * (scr_stride + 8u + w_stride), s),
+          "scratch allocation");
+  auto* scr = static_cast<uint8_t*>(scratch);
+  auto* meta = reinterpret_cast<uint2*>(scr + ch.size * scr_stride);
+  auto* wscr = scr + ch.size * scr_stride + ch.size * 8u;
+  for (uint64_t c0 = 0; c0 < a.nseg; c0 += ch.size) {
+    const CompressArgs c = a.chunk(c0, ch.size);
+    const uint32_t cn = c.nseg;
+    SegOrder ord;
+    cost_order(ctx, s, ord, c);
+    hipLaunchKernelGGL(bitar_hip::zstd_parse_kernel, dim3(cn), dim3(64), 0, s, c.in, c.n, seg, scr,
+                       scr_stride, meta, ord.order);
+    hipLaunchKernelGGL(bitar_hip::zstd_entropy_kernel, dim3(cn), dim3(64), 0, s, c.in, c.n, seg,
+                       scr, scr_stride, meta, wscr, w_stride, ord.order);
+    SegOrder word;  // (the walk's order: sequence counts, most first)
+    word.make(ctx, s, cn, nullptr, [&](uint32_t* keys) {
+      hipLaunchKernelGGL(bitar_hip::walk_key_kernel, dim3((cn + 63) / 64), dim3(64), 0, s, meta,
+                         cn, keys);
+    }, 0, 1);
+    hipLaunchKernelGGL(bitar_hip::zstd_walk_kernel, dim3((cn + 3) / 4), dim3(64), 0, s, scr,
+                       scr_stride, seg, cn, wscr, w_stride, word.order);
+    word.release();
+    hipLaunchKernelGGL(bitar_hip::zstd_emit_kernel, dim3(cn), dim3(64), 0, s, c.in, c.n, seg, scr,
+                       scr_stride, c.slab, c.stride, c.dsts, c.sizes, wscr, w_stride, ord.order);
+  }
+  const hipError_t le = hipGetLastError();
+  HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+  HIP_TRY(le, "compress launch");
+  return 0;
+}
 
 static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const void* d_in,
                          uint64_t n, uint32_t seg, void* d_slab, uint64_t slot_stride,
                          void* const* d_dsts, uint32_t* d_sizes, uint32_t* d_bits = nullptr) {
   if (int r = enter(ctx)) return r;
-  if (codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_DEFLATE &&
-      codec != BITAR_HIP_CODEC_ZSTD && codec != BITAR_HIP_CODEC_DEFLATE_DYNAMIC &&
-      codec != BITAR_HIP_CODEC_LZ4_WIDE && codec != BITAR_HIP_CODEC_SNAPPY &&
-      codec != BITAR_HIP_CODEC_RANS && codec != BITAR_HIP_CODEC_SYMTAB && !column_codec(codec))
-    return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
+  const Codec c = find_codec(codec);
+  if (!c) return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
   if (n == 0) return 0;  // empty input -> no segments (reference device.cc:161-164)
   if (!d_in || (!d_slab && !d_dsts) || !d_sizes) return fail(BITAR_HIP_INVALID, "null buffer");
@@ -673,201 +768,24 @@ static int compress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const
   const uint64_t nseg = (n + seg - 1) / seg;
   if (nseg > 0x7FFFFFFFull) return fail(BITAR_HIP_INVALID, "too many segments");
   hipStream_t s = pick_stream(ctx, stream);
-  const auto* in = static_cast<const uint8_t*>(d_in);
-  auto* slab = static_cast<uint8_t*>(d_slab);
-  auto* dsts = reinterpret_cast<uint8_t* const*>(d_dsts);
-  // cost-ordered dispatch of the segments of [cin, cin + nb): key = distinct byte values in
-  // a 128-byte sample of each segment (incompressible segments, which the parses skip
-  // through and whose stored form is a copy, show the most)
-  auto cost_order = [&](SegOrder& o, const uint8_t* cin, uint64_t nb, uint32_t cn) {
-    return o.make(ctx, s, cn, nullptr, [&](uint32_t* keys) {
-      hipLaunchKernelGGL(bitar_hip::seg_cost_kernel, dim3((cn + 15) / 16), dim3(64), 0, s,
-                         cin, nb, seg, cn, keys);
-    });
-  };
-  const ColumnCodec cc = column_codec(codec);
-  if (cc && cc.family != kAutoPack) {
-    // one streaming kernel, the same work for every segment: plain order (intpack.hip,
-    // fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip, patchpack.hip)
-    hipLaunchKernelGGL(compress_kernel<true>(cc.family, cc.lg), dim3((uint32_t)nseg), dim3(64), 0,
-                       s, in, n, seg, slab, slot_stride, dsts, d_sizes);
+  const CompressArgs a{static_cast<const uint8_t*>(d_in), n, seg, (uint32_t)nseg,
+                       static_cast<uint8_t*>(d_slab), slot_stride,
+                       reinterpret_cast<uint8_t* const*>(d_dsts), d_sizes, d_bits};
+  int r;
+  if (c.column) r = compress_column(s, c.column, a);
+  else switch (codec) {
+    case BITAR_HIP_CODEC_LZ4: r = compress_lz4(ctx, s, false, a); break;
+    case BITAR_HIP_CODEC_LZ4_WIDE: r = compress_lz4(ctx, s, true, a); break;
+    case BITAR_HIP_CODEC_SNAPPY: r = compress_snappy(ctx, s, a); break;
+    case BITAR_HIP_CODEC_DEFLATE: r = compress_deflate(ctx, s, a); break;
+    case BITAR_HIP_CODEC_DEFLATE_DYNAMIC: r = compress_deflate_dynamic(ctx, s, a); break;
+    default: r = compress_zstd(ctx, s, a); break;
   }
-  else if (codec == BITAR_HIP_CODEC_RANS) {
-    // the same again (rans.hip): histogram, table and coder of one segment in one wave; a
-    // segment never fails (the stored form fits every slot)
-    hipLaunchKernelGGL((bitar_hip::column_compress_kernel<bitar_hip::Rans, 1, true>),
-                       dim3((uint32_t)nseg), dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts,
-                       d_sizes);
-  }
-  else if (codec == BITAR_HIP_CODEC_SYMTAB) {
-    // and again (symtab.hip): the table's five generations and the parse of one segment in one
-    // wave; a segment never fails (the stored form fits every slot)
-    hipLaunchKernelGGL((bitar_hip::column_compress_kernel<bitar_hip::SymTab, 1, true>),
-                       dim3((uint32_t)nseg), dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts,
-                       d_sizes);
-  }
-  else if (cc) {
-    // the smallest of the candidates' streams per segment (autopack.hip): RUNPACK straight
-    // into the caller's slots, every later candidate that offers the width (kCandidates,
-    // kColumn) into a stream-ordered scratch slab of its own
-    // with its own sizes (store-less: a segment a later candidate would store gets its size
-    // only, and the select kernel never takes it), then the select kernel.  Chunks of <=
-    // kAutoChunkSegs segments over one allocation.
-    uint32_t extra = 0;  // the candidates after the first
-    for (ColumnFamily f : kCandidates) extra += offers(f, cc.lg) ? 1u : 0u;
-    --extra;
-    const uint64_t scr_stride = bitar_hip_slot_size(codec, seg);
-    const Chunks ch(nseg, kAutoChunkSegs);
-    const bool lean = autopack_storeless();
-    void* scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, extra * ch.size * (scr_stride + 4u), s), "scratch allocation");
-    auto* scr = static_cast<uint8_t*>(scratch);
-    auto* ssz = reinterpret_cast<uint32_t*>(scr + extra * ch.size * scr_stride);
-    for (uint64_t c0 = 0; c0 < nseg; c0 += ch.size) {
-      const uint32_t cn = (uint32_t)(nseg - c0 < ch.size ? nseg - c0 : ch.size);
-      const uint64_t cb = c0 * seg, nb = n - cb < (uint64_t)cn * seg ? n - cb : (uint64_t)cn * seg;
-      uint8_t* cslab = slab ? slab + c0 * slot_stride : nullptr;
-      uint8_t* const* cdsts = dsts ? dsts + c0 : nullptr;
-      const uint8_t* cin = in + cb;
-      uint32_t k = 0;  // the next scratch candidate
-      for (ColumnFamily f : kCandidates) {
-        if (!offers(f, cc.lg)) continue;
-        if (f == kCandidates[0]) {
-          hipLaunchKernelGGL(compress_kernel<true>(f, cc.lg), dim3(cn), dim3(64), 0, s, cin, nb,
-                             seg, cslab, slot_stride, cdsts, d_sizes + c0);
-        } else {
-          const CompressKernel kernel =
-              lean ? compress_kernel<false>(f, cc.lg) : compress_kernel<true>(f, cc.lg);
-          hipLaunchKernelGGL(kernel, dim3(cn), dim3(64), 0, s, cin, nb, seg,
-                             scr + k * ch.size * scr_stride, scr_stride,
-                             (uint8_t* const*)nullptr, ssz + k * ch.size);
-          ++k;
-        }
-      }
-      hipLaunchKernelGGL(bitar_hip::autopack_select_kernel, dim3((cn + 3) / 4), dim3(256), 0, s,
-                         static_cast<const uint8_t*>(scr), scr_stride,
-                         static_cast<const uint32_t*>(ssz), (uint32_t)ch.size, extra + 1u, cn,
-                         cslab, slot_stride, cdsts, d_sizes + c0);
-    }
-    const hipError_t le = hipGetLastError();
-    HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
-    HIP_TRY(le, "compress launch");
-  }
-  else if (codec == BITAR_HIP_CODEC_LZ4 || codec == BITAR_HIP_CODEC_LZ4_WIDE) {
-    SegOrder ord;
-    if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
-    if (codec == BITAR_HIP_CODEC_LZ4)
-      hipLaunchKernelGGL((bitar_hip::lz4_compress_kernel<4096, 10>), dim3((uint32_t)nseg),
-                         dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts, d_sizes,
-                         err_word(ctx, s), ord.order);
-    else
-      hipLaunchKernelGGL((bitar_hip::lz4_compress_kernel<16384, 12>), dim3((uint32_t)nseg),
-                         dim3(64), 0, s, in, n, seg, slab, slot_stride, dsts, d_sizes,
-                         err_word(ctx, s), ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else if (codec == BITAR_HIP_CODEC_SNAPPY) {
-    // the LZ4 parse with the Snappy emitter (snappy.hip), dispatched as LZ4 is; a segment
-    // never fails (the stored form fits every slot), so the kernel takes no error word
-    SegOrder ord;
-    if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
-    hipLaunchKernelGGL(bitar_hip::snappy_compress_kernel, dim3((uint32_t)nseg), dim3(64), 0, s,
-                       in, n, seg, slab, slot_stride, dsts, d_sizes, ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else if (codec == BITAR_HIP_CODEC_DEFLATE) {
-    SegOrder ord;
-    if (int r = cost_order(ord, in, n, (uint32_t)nseg)) return r;
-    if (d_bits)  // (a kernel of its own: bitar_hip_compress keeps its code, compress.hip)
-      hipLaunchKernelGGL(bitar_hip::deflate_compress_bits_kernel, dim3((uint32_t)nseg), dim3(64),
-                         0, s, in, n, seg, slab, slot_stride, dsts, d_sizes, err_word(ctx, s),
-                         ord.order, d_bits);
-    else
-      hipLaunchKernelGGL(bitar_hip::deflate_compress_kernel, dim3((uint32_t)nseg), dim3(64), 0, s,
-                         in, n, seg, slab, slot_stride, dsts, d_sizes, err_word(ctx, s), ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else if (codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC) {
-    // pass 1 (parse -> records + histograms) and pass 2 (codes + emit) through a
-    // stream-ordered scratch per segment (deflate_dyn.hip): 2 KiB plan + the literal stream
-    // (<= seg bytes, 16-B aligned) + 8-byte match records (<= seg / 4: matches are >= 4
-    // bytes); the per-window form (BITAR_DYN_BULK 0) needs 2 KiB + 16 KiB of window masks +
-    // 4-byte records, within the same stride.  Large calls run in chunks of <= kChunkSegs
-    // segments over one scratch allocation, so scratch is bounded whatever the call's size.
-    const uint64_t scr_old = bitar_hip_slot_size(BITAR_HIP_CODEC_DEFLATE, seg) + 2048u + 16384u;
-    const uint64_t scr_bulk = 2048u + ((seg + 15u) & ~15ull) + 8u * ((uint64_t)seg / 4u + 64u);
-    const uint64_t scr_stride = ((scr_old > scr_bulk ? scr_old : scr_bulk) + 15u) & ~15ull;
-    const Chunks ch(nseg);
-    void* scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, ch.size * scr_stride, s), "scratch allocation");
-    auto* scr = static_cast<uint8_t*>(scratch);
-    for (uint64_t c0 = 0; c0 < nseg; c0 += ch.size) {
-      const uint64_t cn = nseg - c0 < ch.size ? nseg - c0 : ch.size;
-      const uint64_t cb = c0 * seg, nb = n - cb < cn * seg ? n - cb : cn * seg;
-      uint8_t* cslab = slab ? slab + c0 * slot_stride : nullptr;
-      uint8_t* const* cdsts = dsts ? dsts + c0 : nullptr;
-      SegOrder ord;
-      if (int r = cost_order(ord, in + cb, nb, (uint32_t)cn)) return r;
-      hipLaunchKernelGGL(bitar_hip::deflate_dyn_parse_kernel, dim3((uint32_t)cn), dim3(64), 0, s,
-                         in + cb, nb, seg, scr, scr_stride, err_word(ctx, s), ord.order);
-      hipLaunchKernelGGL(bitar_hip::deflate_dyn_emit_kernel, dim3((uint32_t)cn), dim3(64), 0, s,
-                         in + cb, nb, seg, static_cast<const uint8_t*>(scr), scr_stride, cslab,
-                         slot_stride, cdsts, d_sizes + c0, err_word(ctx, s), ord.order,
-                         d_bits ? d_bits + c0 : nullptr);
-      if (int r = ord.release()) return r;
-    }
-    const hipError_t le = hipGetLastError();
-    HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
-    HIP_TRY(le, "compress launch");
-  }
-  else {
-    // pass 1 (parse -> literals + sequence records) and pass 2 (entropy coding) through a
-    // stream-ordered scratch: per segment the literal area + records (zstd_compress.hip),
-    // then {nlit, nseq} per segment
-    const uint64_t scr_stride = bitar_hip::zse::scratch_stride(seg);
-    // + the chain-walk scratch (zstd_layout.hip.h: a 5000-byte header with the record, the
-    // literal codes and the FSE tables, then 10 bytes per sequence and 12 per step of <= 64)
-    const uint64_t w_stride = bitar_hip::zse::walk_stride(seg);
-    const Chunks ch(nseg);
-    void* scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, ch.size * (scr_stride + 8u + w_stride), s),
-            "scratch allocation");
-    auto* scr = static_cast<uint8_t*>(scratch);
-    auto* meta = reinterpret_cast<uint2*>(scr + ch.size * scr_stride);
-    auto* wscr = scr + ch.size * scr_stride + ch.size * 8u;
-    for (uint64_t c0 = 0; c0 < nseg; c0 += ch.size) {
-      const uint64_t cn = nseg - c0 < ch.size ? nseg - c0 : ch.size;
-      const uint64_t cb = c0 * seg, nb = n - cb < cn * seg ? n - cb : cn * seg;
-      uint8_t* cslab = slab ? slab + c0 * slot_stride : nullptr;
-      uint8_t* const* cdsts = dsts ? dsts + c0 : nullptr;
-      const uint8_t* cin = in + cb;
-      SegOrder ord;
-      if (int r = cost_order(ord, cin, nb, (uint32_t)cn)) return r;
-      hipLaunchKernelGGL(bitar_hip::zstd_parse_kernel, dim3((uint32_t)cn), dim3(64), 0, s, cin,
-                         nb, seg, scr, scr_stride, meta, ord.order);
-      hipLaunchKernelGGL(bitar_hip::zstd_entropy_kernel, dim3((uint32_t)cn), dim3(64), 0, s, cin,
-                         nb, seg, scr, scr_stride, meta, wscr, w_stride, ord.order);
-      SegOrder word;  // (the walk's order: sequence counts, most first)
-      if (int r = word.make(ctx, s, (uint32_t)cn, nullptr, [&](uint32_t* keys) {
-            hipLaunchKernelGGL(bitar_hip::walk_key_kernel, dim3((uint32_t)((cn + 63) / 64)),
-                               dim3(64), 0, s, meta, (uint32_t)cn, keys);
-          }, 0, 1))
-        return r;
-      hipLaunchKernelGGL(bitar_hip::zstd_walk_kernel, dim3((uint32_t)((cn + 3) / 4)), dim3(64),
-                         0, s, scr, scr_stride, seg, (uint32_t)cn, wscr, w_stride, word.order);
-      if (int r = word.release()) return r;
-      hipLaunchKernelGGL(bitar_hip::zstd_emit_kernel, dim3((uint32_t)cn), dim3(64), 0, s, cin, nb,
-                         seg, scr, scr_stride, cslab, slot_stride, cdsts, d_sizes + c0, wscr,
-                         w_stride, ord.order);
-      if (int r = ord.release()) return r;
-    }
-    const hipError_t le = hipGetLastError();
-    HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
-    HIP_TRY(le, "compress launch");
-  }
+  if (r) return r;
   HIP_TRY(hipGetLastError(), "compress launch");
   return 0;
 }
+}  // extern "C++"
 
 int bitar_hip_compress(bitar_hip_ctx* ctx, void* stream, uint32_t codec, const void* d_in,
                        uint64_t n, uint32_t seg, void* d_slab, uint64_t slot_stride,
@@ -1070,27 +988,16 @@ extern "C" int bitar_hip_path_counters(bitar_hip_ctx* ctx, uint64_t* out, uint32
 
 // segments per wave of zstd_hlit_kernel / zstd_handoff_kernel / zstd_seqdec_kernel (4 / 8 /
 // 16): tuning knobs BITAR_HIP_HLIT_SEGS, BITAR_HIP_HANDOFF_LANES, BITAR_HIP_SEQDEC_SEGS, read once
-static uint32_t pow2_knob(const char* name, uint32_t dflt) {
-  const long x = env_long(name, (long)dflt);
+// (decompress_zstd keeps them in function-local statics)
+static uint32_t pow2_knob(const char* name) {
+  const long x = env_long(name, 16);
   return x >= 16 ? 16u : x >= 8 ? 8u : 4u;
-}
-static uint32_t hlit_segs() {
-  static const uint32_t v = pow2_knob("BITAR_HIP_HLIT_SEGS", 16);
-  return v;
 }
 // (tuning knob: 1 puts the forked single-block literal kernel on the side stream after the
 // multi-block one instead of on the caller's stream after phase A)
 #ifndef BITAR_HLIT1_SIDE
 #define BITAR_HLIT1_SIDE 0
 #endif
-static uint32_t seqdec_segs() {
-  static const uint32_t v = pow2_knob("BITAR_HIP_SEQDEC_SEGS", 16);
-  return v;
-}
-static uint32_t handoff_lanes() {
-  static const uint32_t v = pow2_knob("BITAR_HIP_HANDOFF_LANES", 16);
-  return v;
-}
 
 // the stream paired with the caller's stream s in `list` (created on first use; null if that
 // fails)
@@ -1107,28 +1014,264 @@ static hipStream_t side_stream_for(bitar_hip_ctx* ctx,
 }
 static int stream_after(hipStream_t b, hipStream_t a);
 
+// ---- decompress: one function per format, dispatched by decompress_impl --------------------
+extern "C++" {
+// What every format's function takes (validated by decompress_impl): segment i is sizes[i]
+// bytes at srcs[i] (or slab + i * stride) and decodes to out + i * seg, its length to
+// produced[i].  chunk(): the same for the segments [c0, c0 + most) of the call.
+struct DecompressArgs {
+  const uint8_t* const* srcs;
+  const uint8_t* slab;
+  uint64_t stride;
+  const uint32_t* sizes;
+  uint32_t nseg, seg;
+  uint8_t* out;
+  uint32_t* produced;
+  DecompressArgs chunk(uint64_t c0, uint64_t most) const {
+    const uint32_t cn = (uint32_t)(nseg - c0 < most ? nseg - c0 : most);
+    return {srcs ? srcs + c0 : nullptr, slab ? slab + c0 * stride : nullptr, stride, sizes + c0,
+            cn, seg, out + c0 * seg, produced + c0};
+  }
+};
+
+// A run-time lane count as a template argument: f(Width<W>{}) for the W of the list that n
+// equals, or for the last of the list when n equals none.
+template <uint32_t W>
+using Width = std::integral_constant<uint32_t, W>;
+template <uint32_t W, uint32_t... Rest, class F>
+static void with_width(uint32_t n, F&& f) {
+  if constexpr (sizeof...(Rest) > 0)
+    if (n != W) return with_width<Rest...>(n, f);
+  f(Width<W>{});
+}
+
+// A family's codec: its decoder over every segment, in plain order (a segment's work is its
+// length whatever its coded size).
+// AUTOPACK: each segment to the decoder its tag names (autopack.hip): the route kernel rejects the
+// segments no format claims and sorts the others into one index list per format, with the
+// counts, in a stream-ordered scratch; each format's listed decoder then runs over nseg
+// workgroups of which the first count[f] take a segment.  No host round trip.
+static int decompress_column(bitar_hip_ctx* ctx, hipStream_t s, ColumnCodec cc,
+                             const DecompressArgs& a) {
+  if (cc.family != kAutoPack) {
+    hipLaunchKernelGGL(decompress_kernel<false>(cc.family, cc.lg), dim3(a.nseg), dim3(64), 0, s,
+                       a.srcs, a.slab, a.stride, a.sizes, a.nseg, a.seg, a.out, a.produced,
+                       err_word(ctx, s), (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+    return 0;
+  }
+  const bool lists = autopack_lists();
+  const Chunks ch(a.nseg, kAutoDecChunkSegs);
+  void* scratch = nullptr;
+  if (lists) HIP_TRY(hipMallocAsync(&scratch, 16u * ch.size + 16u, s), "scratch allocation");
+  auto* counts = static_cast<uint32_t*>(scratch);
+  uint32_t* ew = err_word(ctx, s);
+  hipError_t me = hipSuccess;
+  for (uint64_t c0 = 0; c0 < a.nseg && me == hipSuccess; c0 += ch.size) {
+    const DecompressArgs c = a.chunk(c0, ch.size);
+    const uint32_t cn = c.nseg;
+    uint32_t* cl = lists ? counts + 4 : nullptr;
+    if (lists) me = hipMemsetAsync(counts, 0, 16, s);
+    if (me != hipSuccess) break;
+    hipLaunchKernelGGL(bitar_hip::autopack_route_kernel, dim3((cn + 255) / 256), dim3(256), 0, s,
+                       c.srcs, c.slab, c.stride, c.sizes, cn, c.produced, ew, cl, counts);
+    for (uint32_t f = 0; f < kListedDecoders; ++f)
+      hipLaunchKernelGGL(decompress_kernel<true>(f, 0), dim3(cn), dim3(64), 0, s, c.srcs, c.slab,
+                         c.stride, c.sizes, cn, c.seg, c.out, c.produced, ew,
+                         lists ? cl + (uint64_t)f * cn : (const uint32_t*)nullptr,
+                         lists ? counts + f : (const uint32_t*)nullptr);
+  }
+  const hipError_t le = hipGetLastError();
+  if (scratch) HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
+  HIP_TRY(me, "clear counts");
+  HIP_TRY(le, "decompress launch");
+  return 0;
+}
+
+// near-history kernel over every segment, then the far-history kernel over the segments
+// it deferred (lz4_decompress.hip)
+// cost key: the coded size, largest first; incompressible segments (copies) last
+static int decompress_lz4(bitar_hip_ctx* ctx, hipStream_t s, const DecompressArgs& a) {
+  unsigned long long* const stats = stats_of(ctx);
+  SegOrder ord;
+  ord.make(ctx, s, a.nseg, a.sizes, [](uint32_t*) {}, a.seg);
+  for (auto kernel : {bitar_hip::lz4_decompress_kernel<false>, bitar_hip::lz4_decompress_kernel<true>})
+    hipLaunchKernelGGL(kernel, dim3(a.nseg), dim3(64), 0, s, a.srcs, a.slab, a.stride, a.sizes,
+                       a.nseg, a.seg, a.out, a.produced, err_word(ctx, s), stats, ord.order);
+  return 0;
+}
+
+// one kernel (snappy.hip): far history is read back from HBM inside it.  Cost key: the
+// coded size, largest first; stored segments (one literal: copies) last
+static int decompress_snappy(bitar_hip_ctx* ctx, hipStream_t s, const DecompressArgs& a) {
+  SegOrder ord;
+  ord.make(ctx, s, a.nseg, a.sizes, [](uint32_t*) {}, a.seg);
+  hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel<false>, dim3(a.nseg), dim3(64), 0, s,
+                     a.srcs, a.slab, a.stride, a.sizes, a.nseg, a.seg, a.out, a.produced,
+                     err_word(ctx, s), ord.order);
+  return 0;
+}
+
+// lane-per-segment decoder for stored / fixed-Huffman streams first; the wave decoder
+// then takes the segments it deferred (inflate_lanes.hip).  fixed_hint: the caller's id was
+// DEFLATE, not DEFLATE_DYNAMIC, which picks the inflater built for fixed-Huffman streams (9 /
+// 8-bit fast tables, more waves per CU; any stream still decodes, inflate_fixed.hip)
+static int decompress_deflate(bitar_hip_ctx* ctx, hipStream_t s, bool fixed_hint,
+                              const DecompressArgs& a) {
+  const uint32_t L = ctx->inflate_lanes.load(std::memory_order_relaxed);
+  if (L)
+    with_width<32, 16, 8, 4>(L, [&](auto lanes) {
+      hipLaunchKernelGGL(bitar_hip::inflate_lanes_kernel<decltype(lanes)::value>,
+                         dim3((a.nseg + L - 1) / L), dim3(64), 0, s, a.srcs, a.slab, a.stride,
+                         a.sizes, a.nseg, a.seg, a.out, a.produced);
+    });
+  SegOrder ord;
+  ord.make(ctx, s, a.nseg, a.sizes, [](uint32_t*) {}, a.seg);
+  hipLaunchKernelGGL(fixed_hint ? bitar_hip::inflate_fixed_kernel : bitar_hip::inflate_kernel,
+                     dim3(a.nseg), dim3(64), 0, s, a.srcs, a.slab, a.stride, a.sizes, a.nseg, a.seg,
+                     a.out, a.produced, err_word(ctx, s), L ? 1u : 0u, stats_of(ctx), ord.order);
+  return 0;
+}
+
+// lane-per-segment decoder first; the wave-per-segment decoder then takes the segments it
+// deferred (zstd_lanes.hip)
+static int decompress_zstd(bitar_hip_ctx* ctx, hipStream_t s, const DecompressArgs& a) {
+  unsigned long long* const stats = stats_of(ctx);
+  const uint32_t seg = a.seg;
+  const uint32_t L = ctx->zstd_lanes.load(std::memory_order_relaxed);
+  if (L)
+    with_width<64, 32, 16, 8>(L, [&](auto lanes) {
+      hipLaunchKernelGGL(bitar_hip::zstd_lanes_kernel<decltype(lanes)::value>,
+                         dim3((a.nseg + L - 1) / L), dim3(64), 0, s, a.srcs, a.slab, a.stride,
+                         a.sizes, a.nseg, seg, a.out, a.produced);
+    });
+  // The wave decoder hands the sequence sections of its frames' last blocks over through a
+  // stream-ordered scratch (zstd_hand.hip.h: kStride bytes per segment); segments <= 64 KiB
+  // then run FSE chains -> records (zstd_seqdec_kernel, rcap 8-byte records per segment)
+  // -> output (zstd_exec_kernel), the rest the lane executor.  Both scratch buffers are
+  // allocated before any kernel is queued, once, for a chunk of <= kChunkSegs segments.
+  const Chunks ch(a.nseg);
+  const bool seq = ctx->zstd_seq.load(std::memory_order_relaxed) && seg <= 65536;
+  const uint32_t rcap = seg / 3 + 1;  // every valid frame (matches are >= 3 bytes)
+  void* hscr = nullptr;
+  void* recs = nullptr;
+  HIP_TRY(hipMallocAsync(&hscr, ch.size * bitar_hip::zhand::kStride, s), "scratch allocation");
+  if (seq) {
+    const hipError_t e = hipMallocAsync(&recs, ch.size * rcap * 8, s);
+    if (e != hipSuccess) {
+      (void)hipFreeAsync(hscr, s);
+      return hip_fail(e, "scratch allocation");
+    }
+  }
+  uint8_t* hs = static_cast<uint8_t*>(hscr);
+  auto* rp = static_cast<uint64_t*>(recs);
+  uint32_t* ew = err_word(ctx, s);
+  static const uint32_t hs_n = pow2_knob("BITAR_HIP_HLIT_SEGS"),
+                        ho_n = pow2_knob("BITAR_HIP_HANDOFF_LANES"),
+                        sd = pow2_knob("BITAR_HIP_SEQDEC_SEGS");
+  for (uint64_t c0 = 0; c0 < a.nseg; c0 += ch.size) {
+    const DecompressArgs c = a.chunk(c0, ch.size);
+    const uint32_t cn = c.nseg;
+    SegOrder ord;  // (cost key: the compressed size)
+    ord.make(ctx, s, cn, c.sizes, [](uint32_t*) {}, seg);
+    // (multi-block hand-offs -- every block of this engine's frames -- need the two-phase
+    // sequence path; the lane executor takes last blocks only)
+    hipLaunchKernelGGL(bitar_hip::zstd_decompress_kernel, dim3(cn), dim3(64), 0, s, c.srcs, c.slab,
+                       c.stride, c.sizes, cn, seg, c.out, c.produced, ew, L ? 1u : 0u, hs, stats,
+                       ord.order, seq ? 1u : 0u);
+    // N segments per wave and B blocks per segment of the literal and the sequence kernels
+    // (the multi-block kernels (B > 1) take units of 4 blocks: 2 cn of them)
+    auto launch_hlit = [&](hipStream_t s, auto segs, auto blocks, const uint32_t* order) {
+      constexpr uint32_t N = decltype(segs)::value, B = decltype(blocks)::value;
+      hipLaunchKernelGGL((bitar_hip::zstd_hlit_kernel<N, B>),
+                         dim3(((B > 1 ? 2 : 1) * cn + N - 1) / N), dim3(64), 0, s, c.srcs, c.slab,
+                         c.stride, c.sizes, cn, seg, c.out, c.produced, hs, ew, order);
+    };
+    auto launch_seqdec = [&](hipStream_t s, auto segs, auto blocks, const uint32_t* order) {
+      constexpr uint32_t N = decltype(segs)::value, B = decltype(blocks)::value;
+      hipLaunchKernelGGL((bitar_hip::zstd_seqdec_kernel<N, B>),
+                         dim3(((B > 1 ? 2 : 1) * cn + N - 1) / N), dim3(64), 0, s, c.srcs, c.slab,
+                         c.stride, c.sizes, cn, seg, c.produced, hs, rp, rcap, ew, stats, order);
+    };
+    // the literal streams beside the sequences' phase A: one of the two on the aux stream
+    // (zstd_fork 1: the literals there, launched first; 2: phase A there, first)
+    // the multi-block lane kernels take their segments most expensive first (by sequences /
+    // by literals: the column types of a record batch alternate in runs of segments, and
+    // index order would give whole CUs the same kind of segment)
+    SegOrder oseq, olit;
+    if (seq) {
+      oseq.make(ctx, s, 2 * cn, nullptr, [&](uint32_t* keys) {
+        hipLaunchKernelGGL(bitar_hip::hand_key_kernel, dim3((2 * cn + 63) / 64), dim3(64), 0, s,
+                           c.produced, hs, cn, 0u, keys);
+      }, 0, 1);
+      olit.make(ctx, s, 2 * cn, nullptr, [&](uint32_t* keys) {
+        hipLaunchKernelGGL(bitar_hip::hand_key_kernel, dim3((2 * cn + 63) / 64), dim3(64), 0, s,
+                           c.produced, hs, cn, 1u, keys);
+      }, 0, 2);
+    }
+    const uint32_t fork = seq ? ctx->zstd_fork.load(std::memory_order_relaxed) : 0u;
+    hipStream_t aux = fork ? side_stream_for(ctx, ctx->aux_streams, s) : nullptr;
+    if (aux && stream_after(aux, s)) aux = nullptr;
+    // single-block hand-offs (16 segments x 4 streams / chains per wave) and, with the
+    // two-phase path, the multi-block ones (4 segments x 4 blocks x 4 per wave).  Forked
+    // (fork 1), the single-block literal kernel goes on the caller's stream after phase A:
+    // ahead of the multi-block literals on the side stream, its 36 KiB workgroups -- which
+    // exit at once on this engine's multi-block frames -- waited for CU room behind phase A,
+    // and the multi-block literals behind them (1 GiB kind 2: 1.3 ms on the call's path).
+    const bool split = aux && fork == 1;
+    auto hlit1 = [&](hipStream_t s) {
+      with_width<4, 8, 16>(hs_n, [&](auto segs) { launch_hlit(s, segs, Width<1>{}, nullptr); });
+    };
+    auto hlit = [&](hipStream_t s) {
+      if (!split) hlit1(s);
+      if (seq) launch_hlit(s, Width<4>{}, Width<4>{}, olit.order);
+      if (split && BITAR_HLIT1_SIDE) hlit1(s);
+    };
+    auto seqdec = [&](hipStream_t s) {
+      with_width<4, 8, 16>(sd, [&](auto segs) { launch_seqdec(s, segs, Width<1>{}, nullptr); });
+      launch_seqdec(s, Width<4>{}, Width<4>{}, oseq.order);
+    };
+    if (aux && fork == 2) {
+      seqdec(aux);
+      hlit(s);
+    } else {
+      hlit(aux ? aux : s);
+      if (seq) seqdec(s);
+      if (split && !BITAR_HLIT1_SIDE) hlit1(s);
+    }
+    if (seq) {
+      if (aux && stream_after(s, aux)) (void)hipStreamSynchronize(aux);  // (join failed: wait here)
+      hipLaunchKernelGGL(bitar_hip::zstd_exec_kernel, dim3(cn), dim3(64), 0, s, c.srcs, c.slab,
+                         c.stride, cn, seg, c.out, c.produced, hs, rp, rcap, ew, stats, ord.order);
+    }
+    ord.release();
+    oseq.release();
+    olit.release();
+    with_width<4, 8, 16>(ho_n, [&](auto lanes) {
+      constexpr uint32_t N = decltype(lanes)::value;
+      hipLaunchKernelGGL(bitar_hip::zstd_handoff_kernel<N>, dim3((cn + N - 1) / N), dim3(64), 0, s,
+                         c.srcs, c.slab, c.stride, c.sizes, cn, seg, c.out, c.produced, hs, ew);
+    });
+  }
+  const hipError_t le = hipGetLastError();
+  if (recs) (void)hipFreeAsync(recs, s);
+  HIP_TRY(hipFreeAsync(hscr, s), "scratch release");
+  HIP_TRY(le, "decompress launch");
+  return 0;
+}
 
 static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
                            const void* const* d_srcs, const void* d_slab, uint64_t stride,
                            const uint32_t* d_sizes, uint32_t nseg, uint32_t seg, void* d_out,
                            uint64_t capacity, uint32_t* d_produced) {
   if (int r = enter(ctx)) return r;
-  // the caller's FIXED hint picks the inflater built for fixed-Huffman streams (9 / 8-bit
-  // fast tables, more waves per CU; any stream still decodes, inflate_fixed.hip)
-  const bool fixed_hint = codec == BITAR_HIP_CODEC_DEFLATE;
-  if (codec == BITAR_HIP_CODEC_DEFLATE_DYNAMIC) codec = BITAR_HIP_CODEC_DEFLATE;  // same format
-  if (codec == BITAR_HIP_CODEC_LZ4_WIDE) codec = BITAR_HIP_CODEC_LZ4;              // same format
-  // (a column codec's width is in each stream's tag, and under AUTOPACK the format too)
-  const ColumnCodec cc = column_codec(codec);
-  if (!cc &&
-      codec != BITAR_HIP_CODEC_LZ4 && codec != BITAR_HIP_CODEC_SNAPPY &&
-      codec != BITAR_HIP_CODEC_RANS && codec != BITAR_HIP_CODEC_SYMTAB &&
-      codec != BITAR_HIP_CODEC_DEFLATE && codec != BITAR_HIP_CODEC_ZSTD)
-    return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
+  // (DEFLATE_DYNAMIC and LZ4_WIDE decode as DEFLATE and LZ4; a column codec's width is in each
+  // stream's tag, and under AUTOPACK the format too)
+  const Codec c = find_codec(codec);
+  if (!c) return fail(BITAR_HIP_NOT_IMPLEMENTED, "unknown codec");
   if (nseg == 0) return 0;  // reference device.cc:244-246
   // Zstd: a segment may be a whole stock frame of up to kMaxZstdFrame bytes (the wave
   // decoder reads far history from HBM; the Arrow adapter decodes stock IPC bodies so)
-  const uint32_t max_seg = codec == BITAR_HIP_CODEC_ZSTD ? kMaxZstdFrame : kMaxSeg;
+  const uint32_t max_seg = c.format == BITAR_HIP_CODEC_ZSTD ? kMaxZstdFrame : kMaxSeg;
   if (seg == 0 || seg > max_seg)
     return fail(BITAR_HIP_INVALID, "seg must be in [1, " + std::to_string(max_seg) + "]");
   if (capacity < (uint64_t)nseg * seg)  // reference device.cc:248-254
@@ -1139,250 +1282,23 @@ static int decompress_impl(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
     return fail(BITAR_HIP_INVALID, "null buffer");
   if (nseg > 0x7FFFFFFFu) return fail(BITAR_HIP_INVALID, "too many segments");
   hipStream_t s = pick_stream(ctx, stream);
-  unsigned long long* const stats = stats_of(ctx);
-  const auto* srcs = reinterpret_cast<const uint8_t* const*>(d_srcs);
-  const auto* slab = static_cast<const uint8_t*>(d_slab);
-  auto* out = static_cast<uint8_t*>(d_out);
-  if (cc && cc.family != kAutoPack) {
-    hipLaunchKernelGGL(cc.family == kRansPlane ? ransplane_decompress_kernel(cc.lg)
-                                               : decompress_kernel<false>(cc.family),
-                       dim3(nseg), dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out,
-                       d_produced, err_word(ctx, s), (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr);
+  const DecompressArgs a{reinterpret_cast<const uint8_t* const*>(d_srcs),
+                         static_cast<const uint8_t*>(d_slab), stride, d_sizes, nseg, seg,
+                         static_cast<uint8_t*>(d_out), d_produced};
+  int r;
+  if (c.column) r = decompress_column(ctx, s, c.column, a);
+  else switch (c.format) {
+    case BITAR_HIP_CODEC_LZ4: r = decompress_lz4(ctx, s, a); break;
+    case BITAR_HIP_CODEC_SNAPPY: r = decompress_snappy(ctx, s, a); break;
+    // (the caller's FIXED hint: DEFLATE itself, not the DEFLATE_DYNAMIC that decodes as it)
+    case BITAR_HIP_CODEC_DEFLATE: r = decompress_deflate(ctx, s, codec == c.format, a); break;
+    default: r = decompress_zstd(ctx, s, a); break;
   }
-  else if (codec == BITAR_HIP_CODEC_RANS) {
-    // (rans.hip: plain order, a segment's work is its length whatever its coded size)
-    hipLaunchKernelGGL((bitar_hip::column_decompress_kernel<bitar_hip::Rans, false>), dim3(nseg),
-                       dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out, d_produced,
-                       err_word(ctx, s), (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-  }
-  else if (codec == BITAR_HIP_CODEC_SYMTAB) {
-    // (symtab.hip: plain order too)
-    hipLaunchKernelGGL((bitar_hip::column_decompress_kernel<bitar_hip::SymTab, false>), dim3(nseg),
-                       dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out, d_produced,
-                       err_word(ctx, s), (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-  }
-  else if (cc) {
-    // each segment to the decoder its tag names (autopack.hip): the route kernel rejects the
-    // segments no format claims and sorts the others into one index list per format, with the
-    // counts, in a stream-ordered scratch; each format's listed decoder then runs over nseg
-    // workgroups of which the first count[f] take a segment.  No host round trip.
-    const bool lists = autopack_lists();
-    const Chunks ch(nseg, kAutoDecChunkSegs);
-    void* scratch = nullptr;
-    if (lists) HIP_TRY(hipMallocAsync(&scratch, 16u * ch.size + 16u, s), "scratch allocation");
-    auto* counts = static_cast<uint32_t*>(scratch);
-    uint32_t* ew = err_word(ctx, s);
-    hipError_t me = hipSuccess;
-    for (uint64_t c0 = 0; c0 < nseg && me == hipSuccess; c0 += ch.size) {
-      const uint32_t cn = (uint32_t)(nseg - c0 < ch.size ? nseg - c0 : ch.size);
-      const uint8_t* const* csrcs = srcs ? srcs + c0 : nullptr;
-      const uint8_t* cslab = slab ? slab + c0 * stride : nullptr;
-      const uint32_t* csz = d_sizes + c0;
-      uint8_t* cout = out + c0 * seg;
-      uint32_t* cprod = d_produced + c0;
-      uint32_t* cl = lists ? counts + 4 : nullptr;
-      if (lists) me = hipMemsetAsync(counts, 0, 16, s);
-      if (me != hipSuccess) break;
-      hipLaunchKernelGGL(bitar_hip::autopack_route_kernel, dim3((cn + 255) / 256), dim3(256), 0, s,
-                         csrcs, cslab, stride, csz, cn, cprod, ew, cl, counts);
-      for (uint32_t f = 0; f < kListedDecoders; ++f)
-        hipLaunchKernelGGL(decompress_kernel<true>(f), dim3(cn), dim3(64), 0, s, csrcs, cslab,
-                           stride, csz, cn, seg, cout, cprod, ew,
-                           lists ? cl + (uint64_t)f * cn : (const uint32_t*)nullptr,
-                           lists ? counts + f : (const uint32_t*)nullptr);
-    }
-    const hipError_t le = hipGetLastError();
-    if (scratch) HIP_TRY(hipFreeAsync(scratch, s), "scratch release");
-    HIP_TRY(me, "clear counts");
-    HIP_TRY(le, "decompress launch");
-  }
-  else if (codec == BITAR_HIP_CODEC_LZ4)
-  {
-    // near-history kernel over every segment, then the far-history kernel over the segments
-    // it deferred (lz4_decompress.hip)
-    // cost key: the coded size, largest first; incompressible segments (copies) last
-    SegOrder ord;
-    if (int r = ord.make(ctx, s, nseg, d_sizes, [](uint32_t*) {}, seg)) return r;
-    hipLaunchKernelGGL(bitar_hip::lz4_decompress_kernel<false>, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
-                       stats, ord.order);
-    hipLaunchKernelGGL(bitar_hip::lz4_decompress_kernel<true>, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
-                       stats, ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else if (codec == BITAR_HIP_CODEC_SNAPPY) {
-    // one kernel (snappy.hip): far history is read back from HBM inside it.  Cost key: the
-    // coded size, largest first; stored segments (one literal: copies) last
-    SegOrder ord;
-    if (int r = ord.make(ctx, s, nseg, d_sizes, [](uint32_t*) {}, seg)) return r;
-    hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel<false>, dim3(nseg), dim3(64), 0, s, srcs,
-                       slab, stride, d_sizes, nseg, seg, out, d_produced, err_word(ctx, s),
-                       ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else if (codec == BITAR_HIP_CODEC_DEFLATE) {
-    // lane-per-segment decoder for stored / fixed-Huffman streams first; the wave decoder
-    // then takes the segments it deferred (inflate_lanes.hip)
-    const uint32_t L = ctx->inflate_lanes.load(std::memory_order_relaxed);
-    if (L) {
-      const dim3 g((nseg + L - 1) / L);
-#define BITAR_INFL_LANES(N)                                                                  \
-  hipLaunchKernelGGL(bitar_hip::inflate_lanes_kernel<N>, g, dim3(64), 0, s, srcs, slab, stride, \
-                     d_sizes, nseg, seg, out, d_produced)
-      if (L == 32) BITAR_INFL_LANES(32);
-      else if (L == 16) BITAR_INFL_LANES(16);
-      else if (L == 8) BITAR_INFL_LANES(8);
-      else BITAR_INFL_LANES(4);
-#undef BITAR_INFL_LANES
-    }
-    SegOrder ord;
-    if (int r = ord.make(ctx, s, nseg, d_sizes, [](uint32_t*) {}, seg)) return r;
-    hipLaunchKernelGGL(fixed_hint ? bitar_hip::inflate_fixed_kernel : bitar_hip::inflate_kernel,
-                       dim3(nseg), dim3(64), 0, s, srcs, slab, stride, d_sizes, nseg, seg, out,
-                       d_produced, err_word(ctx, s), L ? 1u : 0u, stats, ord.order);
-    if (int r = ord.release()) return r;
-  }
-  else {
-    // lane-per-segment decoder first; the wave-per-segment decoder then takes the segments it
-    // deferred (zstd_lanes.hip)
-    const uint32_t L = ctx->zstd_lanes.load(std::memory_order_relaxed);
-    if (L) {
-      const dim3 g((nseg + L - 1) / L);
-      if (L == 64)
-        hipLaunchKernelGGL(bitar_hip::zstd_lanes_kernel<64>, g, dim3(64), 0, s, srcs, slab,
-                           stride, d_sizes, nseg, seg, out, d_produced);
-      else if (L == 32)
-        hipLaunchKernelGGL(bitar_hip::zstd_lanes_kernel<32>, g, dim3(64), 0, s, srcs, slab,
-                           stride, d_sizes, nseg, seg, out, d_produced);
-      else if (L == 16)
-        hipLaunchKernelGGL(bitar_hip::zstd_lanes_kernel<16>, g, dim3(64), 0, s, srcs, slab,
-                           stride, d_sizes, nseg, seg, out, d_produced);
-      else
-        hipLaunchKernelGGL(bitar_hip::zstd_lanes_kernel<8>, g, dim3(64), 0, s, srcs, slab,
-                           stride, d_sizes, nseg, seg, out, d_produced);
-    }
-    // The wave decoder hands the sequence sections of its frames' last blocks over through a
-    // stream-ordered scratch (zstd_hand.hip.h: kStride bytes per segment); segments <= 64 KiB
-    // then run FSE chains -> records (zstd_seqdec_kernel, rcap 8-byte records per segment)
-    // -> output (zstd_exec_kernel), the rest the lane executor.  Both scratch buffers are
-    // allocated before any kernel is queued, once, for a chunk of <= kChunkSegs segments.
-    const Chunks ch(nseg);
-    const bool seq = ctx->zstd_seq.load(std::memory_order_relaxed) && seg <= 65536;
-    const uint32_t rcap = seg / 3 + 1;  // every valid frame (matches are >= 3 bytes)
-    void* hscr = nullptr;
-    void* recs = nullptr;
-    HIP_TRY(hipMallocAsync(&hscr, ch.size * bitar_hip::zhand::kStride, s), "scratch allocation");
-    if (seq) {
-      const hipError_t e = hipMallocAsync(&recs, ch.size * rcap * 8, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(hscr, s);
-        return hip_fail(e, "scratch allocation");
-      }
-    }
-    uint8_t* hs = static_cast<uint8_t*>(hscr);
-    auto* rp = static_cast<uint64_t*>(recs);
-    uint32_t* ew = err_word(ctx, s);
-    const uint32_t hs_n = hlit_segs(), ho_n = handoff_lanes(), sd = seqdec_segs();
-    for (uint64_t c0 = 0; c0 < nseg; c0 += ch.size) {
-      const uint32_t cn = (uint32_t)(nseg - c0 < ch.size ? nseg - c0 : ch.size);
-      const uint8_t* const* csrcs = srcs ? srcs + c0 : nullptr;
-      const uint8_t* cslab = slab ? slab + c0 * stride : nullptr;
-      const uint32_t* csz = d_sizes + c0;
-      uint8_t* cout = out + c0 * seg;
-      uint32_t* cprod = d_produced + c0;
-      SegOrder ord;  // (cost key: the compressed size; allocation failure = plain order)
-      (void)ord.make(ctx, s, cn, csz, [](uint32_t*) {}, seg);
-      // (multi-block hand-offs -- every block of this engine's frames -- need the two-phase
-      // sequence path; the lane executor takes last blocks only)
-      hipLaunchKernelGGL(bitar_hip::zstd_decompress_kernel, dim3(cn), dim3(64), 0, s, csrcs,
-                         cslab, stride, csz, cn, seg, cout, cprod, ew, L ? 1u : 0u, hs, stats,
-                         ord.order, seq ? 1u : 0u);
-#define BITAR_ZSTD_TAIL(K, N)                                                                 \
-  hipLaunchKernelGGL(bitar_hip::K<N>, dim3((cn + N - 1) / N), dim3(64), 0, s, csrcs, cslab, stride, \
-                     csz, cn, seg, cout, cprod, hs, ew)
-  // (the multi-block kernels (B > 1) take units of 4 blocks: 2 cn of them)
-#define BITAR_HLIT(N, B, O)                                                                   \
-  hipLaunchKernelGGL((bitar_hip::zstd_hlit_kernel<N, B>), dim3(((B > 1 ? 2 : 1) * cn + N - 1) / N), \
-                     dim3(64), 0, s, csrcs, cslab, stride, csz, cn, seg, cout, cprod, hs, ew, O)
-      // the literal streams beside the sequences' phase A: one of the two on the aux stream
-      // (zstd_fork 1: the literals there, launched first; 2: phase A there, first)
-      // the multi-block lane kernels take their segments most expensive first (by sequences /
-      // by literals: the column types of a record batch alternate in runs of segments, and
-      // index order would give whole CUs the same kind of segment)
-      SegOrder oseq, olit;
-      if (seq) {
-        (void)oseq.make(ctx, s, 2 * cn, nullptr, [&](uint32_t* keys) {
-          hipLaunchKernelGGL(bitar_hip::hand_key_kernel, dim3((2 * cn + 63) / 64), dim3(64), 0, s,
-                             cprod, hs, cn, 0u, keys);
-        }, 0, 1);
-        (void)olit.make(ctx, s, 2 * cn, nullptr, [&](uint32_t* keys) {
-          hipLaunchKernelGGL(bitar_hip::hand_key_kernel, dim3((2 * cn + 63) / 64), dim3(64), 0, s,
-                             cprod, hs, cn, 1u, keys);
-        }, 0, 2);
-      }
-      const uint32_t fork = seq ? ctx->zstd_fork.load(std::memory_order_relaxed) : 0u;
-      hipStream_t a = fork ? side_stream_for(ctx, ctx->aux_streams, s) : nullptr;
-      if (a && stream_after(a, s)) a = nullptr;
-      // single-block hand-offs (16 segments x 4 streams / chains per wave) and, with the
-      // two-phase path, the multi-block ones (4 segments x 4 blocks x 4 per wave).  Forked
-      // (fork 1), the single-block literal kernel goes on the caller's stream after phase A:
-      // ahead of the multi-block literals on the side stream, its 36 KiB workgroups -- which
-      // exit at once on this engine's multi-block frames -- waited for CU room behind phase A,
-      // and the multi-block literals behind them (1 GiB kind 2: 1.3 ms on the call's path).
-      const bool split = a && fork == 1;
-      auto hlit1 = [&](hipStream_t s) {
-        if (hs_n == 4) BITAR_HLIT(4, 1, nullptr);
-        else if (hs_n == 8) BITAR_HLIT(8, 1, nullptr);
-        else BITAR_HLIT(16, 1, nullptr);
-      };
-      auto hlit = [&](hipStream_t s) {
-        if (!split) hlit1(s);
-        if (seq) BITAR_HLIT(4, 4, olit.order);
-        if (split && BITAR_HLIT1_SIDE) hlit1(s);
-      };
-      auto seqdec = [&](hipStream_t s) {
-#define BITAR_SEQDEC(N, B, O)                                                                 \
-  hipLaunchKernelGGL((bitar_hip::zstd_seqdec_kernel<N, B>), dim3(((B > 1 ? 2 : 1) * cn + N - 1) / N), \
-                     dim3(64), 0, s, csrcs, cslab, stride, csz, cn, seg, cprod, hs, rp, rcap, ew, \
-                     stats, O)
-        if (sd == 4) BITAR_SEQDEC(4, 1, nullptr);
-        else if (sd == 8) BITAR_SEQDEC(8, 1, nullptr);
-        else BITAR_SEQDEC(16, 1, nullptr);
-        BITAR_SEQDEC(4, 4, oseq.order);
-#undef BITAR_SEQDEC
-      };
-      if (a && fork == 2) {
-        seqdec(a);
-        hlit(s);
-      } else {
-        hlit(a ? a : s);
-        if (seq) seqdec(s);
-        if (split && !BITAR_HLIT1_SIDE) hlit1(s);
-      }
-      if (seq) {
-        if (a && stream_after(s, a)) (void)hipStreamSynchronize(a);  // (join failed: wait here)
-        hipLaunchKernelGGL(bitar_hip::zstd_exec_kernel, dim3(cn), dim3(64), 0, s, csrcs, cslab,
-                           stride, cn, seg, cout, cprod, hs, rp, rcap, ew, stats, ord.order);
-      }
-      (void)ord.release();
-      (void)oseq.release();
-      (void)olit.release();
-      if (ho_n == 4) BITAR_ZSTD_TAIL(zstd_handoff_kernel, 4);
-      else if (ho_n == 8) BITAR_ZSTD_TAIL(zstd_handoff_kernel, 8);
-      else BITAR_ZSTD_TAIL(zstd_handoff_kernel, 16);
-#undef BITAR_ZSTD_TAIL
-#undef BITAR_HLIT
-    }
-    const hipError_t le = hipGetLastError();
-    if (recs) (void)hipFreeAsync(recs, s);
-    HIP_TRY(hipFreeAsync(hscr, s), "scratch release");
-    HIP_TRY(le, "decompress launch");
-  }
+  if (r) return r;
   HIP_TRY(hipGetLastError(), "decompress launch");
   return 0;
 }
+}  // extern "C++"
 
 int bitar_hip_decompress(bitar_hip_ctx* ctx, void* stream, uint32_t codec,
                          const void* const* d_srcs, const uint32_t* d_sizes, uint32_t nseg,
@@ -1649,20 +1565,19 @@ int bitar_hip_snappy_decompress_joined(bitar_hip_ctx* ctx, void* stream, const v
   hipStream_t s = pick_stream(ctx, stream);
   // cost key: the fragment's coded size, as the slab decode's
   SegOrder ord;
-  if (int r = ord.make(
-          ctx, s, nfrag, nullptr,
-          [&](uint32_t* keys) {
-            hipLaunchKernelGGL(bitar_hip::snappy_joined_key_kernel, dim3((nfrag + 255) / 256),
-                               dim3(256), 0, s, d_starts, nfrag, keys);
-          },
-          kSnappyBlock))
-    return r;
+  ord.make(
+      ctx, s, nfrag, nullptr,
+      [&](uint32_t* keys) {
+        hipLaunchKernelGGL(bitar_hip::snappy_joined_key_kernel, dim3((nfrag + 255) / 256),
+                           dim3(256), 0, s, d_starts, nfrag, keys);
+      },
+      kSnappyBlock);
   hipLaunchKernelGGL(bitar_hip::snappy_decompress_kernel<true>, dim3(nfrag), dim3(64), 0, s,
                      reinterpret_cast<const uint8_t* const*>(d_starts),
                      static_cast<const uint8_t*>(d_joined), n, (const uint32_t*)nullptr, nfrag,
                      (uint32_t)len, static_cast<uint8_t*>(d_out), d_produced, err_word(ctx, s),
                      ord.order);
-  if (int r = ord.release()) return r;
+  ord.release();
   HIP_TRY(hipGetLastError(), "decompress launch");
   return 0;
 }

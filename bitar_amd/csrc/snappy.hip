@@ -14,6 +14,7 @@
 // copy-1 (2 bytes: 4 <= len <= 11, offset < 2048) or a copy-2 (3 bytes: len <= 64, 16-bit
 // offset).  A literal and the copy after it are separate elements, so a sequence costs two
 // chain steps in the decoder where LZ4 has one token.
+#include "kernels.hip.h"
 #include "order.hip.h"
 #include "stream_ring.hip.h"
 #include "window_parse.hip.h"

@@ -1,4 +1,5 @@
 // util_kernels.hip -- frame packing (prefix sum + gather) and the synthetic-input generator.
+#include "kernels.hip.h"
 #include "order.hip.h"
 #include "wave.hip.h"
 

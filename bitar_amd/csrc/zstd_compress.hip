@@ -17,6 +17,7 @@
 //                        choice and FSE tables (one lane); then the literal streams and the
 //                        sequence bitstream, each lane placing its bit field by a prefix
 //                        sum into the LDS output ring.
+#include "kernels.hip.h"
 #include "huffman.hip.h"
 #include "zstd_layout.hip.h"
 #include "window_parse.hip.h"

@@ -11,6 +11,7 @@
 // construction allows it.  Huffman-coded literals are decoded into the tail of the
 // segment's output slot and copied from there by the sequence executor: output writes never
 // overtake the literal reads (op <= cap - remaining literals).
+#include "kernels.hip.h"
 #include "stream_ring.hip.h"
 #include "zstd_hand.hip.h"
 

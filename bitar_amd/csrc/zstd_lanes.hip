@@ -23,6 +23,7 @@
 // content size (or the capacity when the frame does not state it).  Raw and RLE blocks,
 // where lanes would copy up to 64 KiB each, are instead copied by the whole wave, one
 // lane's block after another, with coalesced 16-B accesses.
+#include "kernels.hip.h"
 #include "lane_copy.hip.h"
 #include "zstd_hand.hip.h"
 

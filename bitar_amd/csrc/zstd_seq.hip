@@ -27,6 +27,7 @@
 // known -- a symbolic one, kSym | k << 17 | (2^17 - 1 - d) = "history slot k at the block's
 // start, minus d" (the repeat offset r0 - 1 of RFC 8878 3.1.2.5 is then the same subtraction
 // for both forms); zstd_exec_kernel resolves them block by block.
+#include "kernels.hip.h"
 #include "lane_copy.hip.h"
 #include "stream_ring.hip.h"
 #include "zstd_hand.hip.h"
