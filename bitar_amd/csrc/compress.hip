@@ -17,9 +17,14 @@
 //   DEFLATE: every position lane contributes its literal code or its match symbol; codes
 //        are placed by a prefix sum of bit lengths and OR-ed into an LDS bit ring.
 #include "kernels.hip.h"
+#include "order.hip.h"
 #include "window_parse.hip.h"
 
 namespace bitar_hip {
+
+#if BITAR_LAUNCH_TIMELINE  // probe builds only (order.hip.h)
+BITAR_TIMELINE_BUFFER(g_lz4c_timeline, bitar_hip_timeline_compress)
+#endif
 
 namespace cmp {
 
@@ -695,10 +700,20 @@ __global__ __launch_bounds__(64) BITAR_LZ4C_ATTR void lz4_compress_kernel(
   __shared__ __attribute__((aligned(16))) uint16_t table[(1u << HLOG) + 8];
   __shared__ __attribute__((aligned(16))) uint8_t inring[RING + kInPad];
   __shared__ __attribute__((aligned(16))) Lz4Lds olds;
+#if BITAR_LAUNCH_TIMELINE
+  const unsigned long long tl_t0 = wall_clock64();
+#endif
   // cost-ordered dispatch (seg_order_kernel): workgroup b compresses segment order[b]
-  const uint32_t i_seg = order ? order[blockIdx.x] : blockIdx.x;
+  // (priority lanes, order.hip.h: the fast parse's orders carry kLaneTag on the fast lane; the
+  // wide parse has none and keeps the code it had)
+  constexpr bool kLanes = kLanePrio != 0 && RING == kIn;
+  const uint32_t ord_b = order ? order[blockIdx.x] : blockIdx.x;
+  const uint32_t i_seg = kLanes && order ? ord_b & ~kLaneTag : ord_b;
   const uint64_t seg_off = (uint64_t)i_seg * seg;
   if (seg_off >= n_total) return;
+  // the slots that run one heavy segment more than the others issue first
+  if constexpr (kLanes)
+    if (order && (ord_b & kLaneTag)) __builtin_amdgcn_s_setprio(kLanePrio);
   const uint32_t n = (uint32_t)((n_total - seg_off) < seg ? (n_total - seg_off) : seg);
   Lz4Out o;
   o.init(&olds, global_ptr(dsts ? dsts[i_seg] : slab + (uint64_t)i_seg * slot_stride), slot_stride);
@@ -716,6 +731,9 @@ __global__ __launch_bounds__(64) BITAR_LZ4C_ATTR void lz4_compress_kernel(
     sizes[i_seg] = o.overflow ? 0xFFFFFFFFu : o.op;
     if (o.overflow) atomicOr(err, 2u);
   }
+#if BITAR_LAUNCH_TIMELINE
+  timeline_record(g_lz4c_timeline, blockIdx.x, i_seg, tl_t0);
+#endif
 }
 
 template __global__ void lz4_compress_kernel<cmp::kIn, cmp::kHashLog>(

@@ -45,7 +45,7 @@ __global__ void seg_cost_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, ui
 __global__ void order_hist_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
                                   uint32_t*);
 __global__ void order_scatter_kernel(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                                     uint32_t, const uint32_t*, uint32_t*);
+                                     uint32_t, const uint32_t*, uint32_t*, uint32_t, uint32_t);
 __global__ void deflate_compress_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*, uint64_t,
                                         uint8_t* const*, uint32_t*, uint32_t*, const uint32_t*);
 __global__ void deflate_compress_bits_kernel(const uint8_t*, uint64_t, uint32_t, uint8_t*,

@@ -28,6 +28,7 @@
 //   Matches reaching further back than the ring read HBM, behind a lazily placed fence.
 //   Literal runs >= kLongLit bypass the ring and stream HBM -> HBM (wave_copy_global).
 #include "kernels.hip.h"
+#include "order.hip.h"  // (the launch timeline of probe builds)
 #include "stream_ring.hip.h"
 
 #include <type_traits>
@@ -46,7 +47,9 @@
 
 namespace bitar_hip {
 
-
+#if BITAR_LAUNCH_TIMELINE  // probe builds only (order.hip.h)
+BITAR_TIMELINE_BUFFER(g_lz4d_timeline, bitar_hip_timeline_decompress)
+#endif
 
 namespace lz4d {
 
@@ -309,6 +312,9 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
   uint8_t* ring = lds;
   uint8_t* win = lds + kRing;
   if (blockIdx.x >= nseg) return;
+#if BITAR_LAUNCH_TIMELINE
+  const unsigned long long tl_t0 = wall_clock64();
+#endif
   // cost-ordered dispatch (seg_order_kernel): workgroup b decodes segment order[b]
   const uint32_t i = order ? order[blockIdx.x] : blockIdx.x;
   if (FARK && produced[i] != kDefer) return;
@@ -862,6 +868,9 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(
     produced[i] = 0xFFFFFFFFu;
     atomicOr(err, 1u);
   }
+#if BITAR_LAUNCH_TIMELINE
+  if (!FARK) timeline_record(g_lz4d_timeline, blockIdx.x, i, tl_t0);
+#endif
 }
 
 template __global__ void lz4_decompress_kernel<false>(const uint8_t* const*, const uint8_t*,

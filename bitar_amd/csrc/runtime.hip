@@ -40,6 +40,10 @@ struct bitar_hip_ctx {
   std::atomic<uint32_t> inflate_lanes{4}, zstd_lanes{16}, zstd_seq{1}, count_paths{0};
   std::atomic<uint32_t> zstd_fork{1};  // Zstd literals beside phase A (decompress_zstd)
   std::atomic<uint32_t> cost_order{1};  // LZ4: dispatch the estimated most expensive segments first
+  // priority lanes (order.hip.h): the device's CUs, and the resident workgroups of the fast
+  // LZ4 compressor, queried on first use (0: not yet)
+  uint32_t cus = 0;
+  std::atomic<uint32_t> lane_slots{0};
   std::mutex mu;              // guards `words` and `order_scratch`
   std::vector<std::pair<hipStream_t, uint32_t>> words;  // stream -> error word index
   // cost-ordered dispatch scratch of the context's own streams (and the default stream),
@@ -192,6 +196,7 @@ int bitar_hip_open(int device, const bitar_hip_config* cfg, bitar_hip_ctx** out)
   HIP_TRY(hipSetDevice(device), "hipSetDevice");
   auto* ctx = new bitar_hip_ctx();
   ctx->device = device;
+  ctx->cus = (uint32_t)prop.multiProcessorCount;
   for (uint32_t q = 0; q < nstreams; ++q) {
     hipStream_t s;
     hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -490,9 +495,12 @@ struct SegOrder {
   // slot: which of the stream's cached scratch areas (a call holding two orders at once
   // uses slots 0 and 1).  The scratch is allocated once per stream and grown on demand, so
   // steady-state calls queue no allocation.
+  // cut, slots: the priority lanes (order.hip.h: H = the segments with keys below `cut`, S =
+  // slots): the fast lane's entries of the order carry kLaneTag, which only the LZ4 kernels
+  // know; slots == 0 for every kernel without lanes.
   template <class F>
   void make(bitar_hip_ctx* ctx, hipStream_t s, uint32_t nseg, const uint32_t* csizes, F key,
-            uint32_t seg = 0, int slot = 0) {
+            uint32_t seg = 0, int slot = 0, uint32_t cut = 0, uint32_t slots = 0) {
     if (!ctx->cost_order.load(std::memory_order_relaxed) || nseg < kOrderMinSegs) return;
     const uint32_t tile = bitar_hip::order_tile(nseg);
     const uint32_t ntiles = (nseg + tile - 1) / tile;
@@ -539,7 +547,7 @@ struct SegOrder {
     hipLaunchKernelGGL(bitar_hip::order_hist_kernel, dim3(ntiles), dim3(64), 0, s, keys, csizes,
                        seg, nseg, tile, hist);
     hipLaunchKernelGGL(bitar_hip::order_scatter_kernel, dim3(ntiles), dim3(64), 0, s, keys,
-                       csizes, seg, nseg, tile, ntiles, hist, order);
+                       csizes, seg, nseg, tile, ntiles, hist, order, cut, slots);
   }
   // after the last launch that reads the order has been queued
   void release() {
@@ -581,12 +589,59 @@ struct CompressArgs {
 // cost-ordered dispatch of the segments of a call or chunk: key = distinct byte values in a
 // 128-byte sample of each segment (incompressible segments, which the parses skip through and
 // whose stored form is a copy, show the most)
-static void cost_order(bitar_hip_ctx* ctx, hipStream_t s, SegOrder& o, const CompressArgs& a) {
+// (slots != 0: with the priority lanes' tags, heavy = keys below kCheapKey)
+static void cost_order(bitar_hip_ctx* ctx, hipStream_t s, SegOrder& o, const CompressArgs& a,
+                       uint32_t slots = 0) {
   o.make(ctx, s, a.nseg, nullptr, [&](uint32_t* keys) {
     hipLaunchKernelGGL(bitar_hip::seg_cost_kernel, dim3((a.nseg + 15) / 16), dim3(64), 0, s, a.in,
                        a.n, a.seg, a.nseg, keys);
-  });
+  }, 0, 0, slots ? bitar_hip::kCheapKey : 0u, slots);
 }
+
+// Priority lanes (order.hip.h): the workgroups of `kernel` (one wave, no
+// dynamic LDS) that the device holds at once, asked of the runtime once per context and
+// kernel.  0 -- lanes compiled out, a call too small for an order, or the query failed --
+// means no lanes: every workgroup runs at priority 0.
+// Lanes are for a launch that has the device to itself.  Beside another queue pair's launch
+// the tail is filled by that launch's waves anyway, and the lanes' priority competes with
+// them (the four-stream record batch measured 0.7 % slower with lanes).  A
+// context's queue-pair streams exist to run calls side by side, so a call on one of several
+// is taken to have siblings and gets no lanes.  This is a convention, not a check of what the
+// device is doing: concurrent calls on streams of the caller's own (torch streams, say) are
+// not seen and get lanes, the configuration that measured slower.  (Asking the other streams
+// with hipStreamQuery instead cost a synchronous call ~15 us of host time and would not see
+// foreign streams either.)
+static bool alone_by_convention(bitar_hip_ctx* ctx, hipStream_t s) {
+  if (ctx->streams.size() < 2) return true;
+  for (hipStream_t q : ctx->streams)
+    if (q == s) return false;
+  return true;
+}
+template <class K>
+static uint32_t lane_slots(bitar_hip_ctx* ctx, hipStream_t s, K kernel, uint32_t nseg) {
+  // (a probe build asks too: scripts/launch_timeline.py prints the answer)
+  if ((!bitar_hip::kLanePrio && !BITAR_LAUNCH_TIMELINE) || nseg < kOrderMinSegs) return 0;
+  if (nseg > bitar_hip::kLaneTag) return 0;  // (the tag is the segment index's top bit)
+  if (!ctx->cost_order.load(std::memory_order_relaxed) || !alone_by_convention(ctx, s)) return 0;
+  uint32_t v = ctx->lane_slots.load(std::memory_order_relaxed);
+  if (!v) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    v = (uint32_t)(per_cu > 0 ? per_cu : 0) * ctx->cus;
+    ctx->lane_slots.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+#if BITAR_LAUNCH_TIMELINE
+// probe builds: the slot count the context found for the fast compressor (0: not asked yet)
+extern "C" __attribute__((visibility("default"))) uint32_t bitar_hip_timeline_slots(
+    bitar_hip_ctx* ctx) {
+  return ctx ? ctx->lane_slots.load(std::memory_order_relaxed) : 0u;
+}
+#endif
 
 // A family's codec: one streaming kernel, the same work for every segment: plain order
 // (intpack.hip, fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip,
@@ -645,12 +700,13 @@ static int compress_column(hipStream_t s, ColumnCodec cc, const CompressArgs& a)
 
 // LZ4 blocks from the fast parse (4 KiB ring) or the wide one (16 KiB)
 static int compress_lz4(bitar_hip_ctx* ctx, hipStream_t s, bool wide, const CompressArgs& a) {
+  const auto kernel = wide ? bitar_hip::lz4_compress_kernel<16384, 12>
+                           : bitar_hip::lz4_compress_kernel<4096, 10>;
   SegOrder ord;
-  cost_order(ctx, s, ord, a);
-  hipLaunchKernelGGL((wide ? bitar_hip::lz4_compress_kernel<16384, 12>
-                           : bitar_hip::lz4_compress_kernel<4096, 10>),
-                     dim3(a.nseg), dim3(64), 0, s, a.in, a.n, a.seg, a.slab, a.stride, a.dsts,
-                     a.sizes, err_word(ctx, s), ord.order);
+  // (lanes for the fast parse only: the wide parse's leg did not gain)
+  cost_order(ctx, s, ord, a, wide ? 0u : lane_slots(ctx, s, kernel, a.nseg));
+  hipLaunchKernelGGL(kernel, dim3(a.nseg), dim3(64), 0, s, a.in, a.n, a.seg, a.slab, a.stride,
+                     a.dsts, a.sizes, err_word(ctx, s), ord.order);
   return 0;
 }
 

@@ -372,9 +372,11 @@ __global__ __launch_bounds__(64) void order_scatter_kernel(const uint32_t* __res
                                                            uint32_t seg, uint32_t nseg,
                                                            uint32_t tile, uint32_t ntiles,
                                                            const uint32_t* __restrict__ hist,
-                                                           uint32_t* __restrict__ order) {
+                                                           uint32_t* __restrict__ order,
+                                                           uint32_t cut, uint32_t slots) {
   static_assert(kOrderBins == 4 * kWave, "four bins per lane");
   __shared__ uint32_t base[kOrderBins];
+  __shared__ uint32_t heavy;  // H of the priority lanes (order.hip.h)
   const uint32_t lane = lane_id(), me = blockIdx.x;
   // lane l owns bins 4l .. 4l + 3: their totals and the counts of the tiles before this one
   uint32_t tot[4] = {0, 0, 0, 0}, pre[4] = {0, 0, 0, 0};
@@ -399,13 +401,26 @@ __global__ __launch_bounds__(64) void order_scatter_kernel(const uint32_t* __res
   uint32_t run = incl - s4;
 #pragma unroll
   for (uint32_t j = 0; j < 4; ++j) {
+    // the priority lanes (order.hip.h lane_prio): H = the segments with keys below `cut`,
+    // which the order puts first
+    if (4 * lane + j == cut) heavy = run;
     base[4 * lane + j] = run + pre[j];
     run += tot[j];
   }
   __syncthreads();
+  // lanes: `slots` resident workgroups of the kernel that takes this order (0: it has no
+  // lanes), and more heavy segments than one round of them
+  const uint32_t H = heavy;
+  const bool lanes = kLanePrio != 0 && slots != 0 && H > slots;
   order_runs(keys, csizes, seg, nseg, tile, [&](uint32_t key, uint32_t start, uint32_t cnt) {
     const uint32_t pos = atomicAdd(&base[key], cnt);
-    for (uint32_t j = 0; j < cnt; ++j) order[pos + j] = start + j;
+    if (lanes) {
+      // the fast lane's dispatch indices carry kLaneTag on their segment
+      for (uint32_t j = 0; j < cnt; ++j)
+        order[pos + j] = (start + j) | (lane_prio(pos + j, H, slots) ? kLaneTag : 0u);
+    } else {
+      for (uint32_t j = 0; j < cnt; ++j) order[pos + j] = start + j;
+    }
   });
 }
 
