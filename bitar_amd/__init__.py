@@ -60,6 +60,12 @@ SNAPPY_NO_SERIAL_FINISH = 0x80000000
 FLAG_INFLATE_WAVE_ONLY, FLAG_ZSTD_WAVE_ONLY, FLAG_ZSTD_LANE_EXEC, FLAG_COUNT_PATHS = 1, 2, 4, 8
 FLAG_PLAIN_ORDER = 0x10  # segment i is workgroup i (no cost-ordered dispatch; same output)
 FLAG_ZSTD_SERIAL = 0x20  # Zstd literals and phase A in series (default: side by side)
+# bitar_hip_debug_order: the modes, the slot count "what an LZ4 compress call would get", the tag
+# of a fast lane's entry, and the status of a call that runs in plain order
+ORDER_COMPRESS_KEY, ORDER_DECOMPRESS_KEY, ORDER_CALLER_KEYS = 0, 1, 2
+ORDER_SLOTS_CALL = 0xFFFFFFFF
+ORDER_LANE_TAG = 0x80000000
+NO_ORDER = 1
 # bitar_hip_path_counter indices
 PATHS = ("inflate_wave", "inflate_wave_reject", "inflate_batch_segs", "inflate_batches",
          "zstd_wave", "zstd_handed", "zstd_seqdec", "zstd_seqdec_reject", "zstd_exec",
@@ -143,6 +149,8 @@ def lib():
         "bitar_hip_crc32_combine": (i32, [vp, vp, vp, u64, u32, u32, vp]),
         "bitar_hip_filter_apply": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
         "bitar_hip_filter_invert": (i32, [vp, vp, u32, u32, vp, u64, u32, vp, u32, vp]),
+        "bitar_hip_debug_order": (i32, [vp, vp, u32, vp, u64, u32, vp, u32, u32, u32, vp, vp,
+                                        ctypes.POINTER(u32)]),
         "bitar_hip_snappy_join": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp]),
         "bitar_hip_snappy_split": (i32, [vp, vp, vp, u64, u64, u32, vp, vp, vp]),
         "bitar_hip_snappy_decompress_joined": (i32, [vp, vp, vp, u64, u64, vp, vp, u64, vp]),
@@ -168,7 +176,8 @@ ABI_SYMBOLS = ("bitar_hip_abi_version", "bitar_hip_last_error", "bitar_hip_devic
                "bitar_hip_set_decoder_options", "bitar_hip_path_counters",
                "bitar_hip_compress_host", "bitar_hip_decompress_host",
                "bitar_hip_compress_bits", "bitar_hip_deflate_join", "bitar_hip_deflate_split",
-               "bitar_hip_crc32_combine", "bitar_hip_filter_apply", "bitar_hip_filter_invert")
+               "bitar_hip_crc32_combine", "bitar_hip_filter_apply", "bitar_hip_filter_invert",
+               "bitar_hip_debug_order")
 # every symbol include/bitar_hip_snappy.h declares (whole-buffer raw Snappy streams: additive, a
 # header of their own; checked by tests/test_gpu_snappy_codec.py)
 SNAPPY_STREAM_SYMBOLS = ("bitar_hip_snappy_join", "bitar_hip_snappy_split",
@@ -497,6 +506,26 @@ class Engine:
         check(lib().bitar_hip_lz4_chain(self.ctx, self._stream(stream), _ptr(src), src_len,
                                         _ptr(blocks), nblocks, _ptr(out), capacity,
                                         _ptr(produced)))
+
+    def debug_order(self, mode, nseg, data=None, n=0, seg=0, values=None, cut=0, slots=0,
+                    keys=False, stream=None):
+        """the dispatch order a call of nseg segments builds (bitar_hip_debug_order), for tests:
+        -> (order, keys, slots_used).  order: int32 HBM tensor of nseg entries, the fast lanes'
+        tagged with ORDER_LANE_TAG (the sign bit), or None where the call runs in plain order;
+        keys (keys=True, not for ORDER_DECOMPRESS_KEY): int32 HBM tensor, else None.
+        ORDER_COMPRESS_KEY reads n bytes of `data` (a uint8 tensor or an address) in segments of
+        seg; the other modes read `values` (int32 tensor: compressed sizes, or keys)."""
+        t = self.torch
+        order = self.empty(max(nseg, 1), dtype=t.int32)
+        kout = self.empty(max(nseg, 1), dtype=t.int32) if keys else None
+        used = ctypes.c_uint32(0)
+        rc = lib().bitar_hip_debug_order(self.ctx, self._stream(stream), mode, _ptr(data), n, seg,
+                                         _ptr(values), nseg, cut, slots, _ptr(order), _ptr(kout),
+                                         ctypes.byref(used))
+        if rc == NO_ORDER:
+            return None, None, used.value
+        check(rc)
+        return order[:nseg], kout[:nseg] if keys else None, used.value
 
     def sync(self, stream=None):
         s = self._stream(stream) if stream is not False else None

@@ -490,6 +490,7 @@ struct SegOrder {
   void* transient = nullptr;  // a foreign stream's scratch (freed by release(), stream-ordered)
   hipStream_t tstream = nullptr;
   uint32_t* order = nullptr;  // null: plain order
+  const uint32_t* keys = nullptr;  // the keys the sort read (null: none made, or csizes given)
   // order = argsort of the keys: keys[i] written by `key` (a launch), or -- csizes given --
   // the compressed sizes' key computed by the sort itself (decompress; seg: the segment size).
   // slot: which of the stream's cached scratch areas (a call holding two orders at once
@@ -540,13 +541,14 @@ struct SegOrder {
       }
     }
     order = static_cast<uint32_t*>(transient ? transient : e->p);
-    uint32_t* keys = csizes ? nullptr : order + nseg;
+    uint32_t* const kbuf = csizes ? nullptr : order + nseg;
+    keys = kbuf;
     auto* hist = reinterpret_cast<uint32_t*>(
         (reinterpret_cast<uintptr_t>(order + 2ull * nseg) + 15) & ~(uintptr_t)15);
-    if (keys) key(keys);
-    hipLaunchKernelGGL(bitar_hip::order_hist_kernel, dim3(ntiles), dim3(64), 0, s, keys, csizes,
+    if (kbuf) key(kbuf);
+    hipLaunchKernelGGL(bitar_hip::order_hist_kernel, dim3(ntiles), dim3(64), 0, s, kbuf, csizes,
                        seg, nseg, tile, hist);
-    hipLaunchKernelGGL(bitar_hip::order_scatter_kernel, dim3(ntiles), dim3(64), 0, s, keys,
+    hipLaunchKernelGGL(bitar_hip::order_scatter_kernel, dim3(ntiles), dim3(64), 0, s, kbuf,
                        csizes, seg, nseg, tile, ntiles, hist, order, cut, slots);
   }
   // after the last launch that reads the order has been queued
@@ -866,6 +868,57 @@ int bitar_hip_compress_bits(bitar_hip_ctx* ctx, void* stream, uint32_t codec, co
   if (n && !d_slab) return fail(BITAR_HIP_INVALID, "null d_slab");
   return compress_impl(ctx, stream, codec, d_in, n, seg, d_slab, slot_stride, nullptr, d_sizes,
                        d_bits);
+}
+
+// The dispatch order of a call, copied out for tests (tests/test_gpu_order.py): built by the
+// code the codecs run -- SegOrder::make, through cost_order() for the compress key, with
+// lane_slots() of the fast LZ4 compressor for BITAR_HIP_ORDER_SLOTS_CALL -- and read back in
+// stream order before the scratch is released.  Nothing here launches the sort itself.
+int bitar_hip_debug_order(bitar_hip_ctx* ctx, void* stream, uint32_t mode, const void* d_in,
+                          uint64_t n, uint32_t seg, const uint32_t* d_values, uint32_t nseg,
+                          uint32_t cut, uint32_t slots, uint32_t* d_order, uint32_t* d_keys,
+                          uint32_t* slots_used) {
+  if (int r = enter(ctx)) return r;
+  if (slots_used) *slots_used = 0;
+  if (mode > BITAR_HIP_ORDER_CALLER_KEYS) return fail(BITAR_HIP_INVALID, "unknown order mode");
+  if (cut >= bitar_hip::kOrderBins) return fail(BITAR_HIP_INVALID, "cut must be below 256");
+  if (nseg > bitar_hip::kLaneTag)
+    return fail(BITAR_HIP_INVALID, "too many segments (the lane tag is the index's top bit)");
+  if (!d_order) return fail(BITAR_HIP_INVALID, "null d_order");
+  const bool compress = mode == BITAR_HIP_ORDER_COMPRESS_KEY;
+  if (compress) {
+    if (seg == 0 || seg > kMaxSeg) return fail(BITAR_HIP_INVALID, "seg must be in [1, 65536]");
+    if (!d_in || !n) return fail(BITAR_HIP_INVALID, "null or empty input");
+    if ((n + seg - 1) / seg != nseg) return fail(BITAR_HIP_INVALID, "nseg must be ceil(n / seg)");
+  } else {
+    if (!d_values) return fail(BITAR_HIP_INVALID, "null d_values");
+    if (mode == BITAR_HIP_ORDER_DECOMPRESS_KEY && (seg == 0 || d_keys))
+      return fail(BITAR_HIP_INVALID, "the decompress key needs seg and keeps no key array");
+  }
+  hipStream_t s = pick_stream(ctx, stream);
+  if (slots == BITAR_HIP_ORDER_SLOTS_CALL)
+    slots = lane_slots(ctx, s, bitar_hip::lz4_compress_kernel<4096, 10>, nseg);
+  if (slots_used) *slots_used = slots;
+  SegOrder ord;
+  if (compress) {
+    const CompressArgs a{static_cast<const uint8_t*>(d_in), n, seg, nseg, nullptr, 0, nullptr,
+                         nullptr, nullptr};
+    cost_order(ctx, s, ord, a, slots);  // (its cut: kCheapKey with slots, else 0)
+  } else if (mode == BITAR_HIP_ORDER_DECOMPRESS_KEY) {
+    ord.make(ctx, s, nseg, d_values, [](uint32_t*) {}, seg, 0, cut, slots);
+  } else {
+    ord.make(ctx, s, nseg, nullptr, [&](uint32_t* keys) {
+      (void)hipMemcpyAsync(keys, d_values, 4ull * nseg, hipMemcpyDeviceToDevice, s);
+    }, 0, 0, cut, slots);
+  }
+  if (!ord.order) return BITAR_HIP_NO_ORDER;
+  HIP_TRY(hipMemcpyAsync(d_order, ord.order, 4ull * nseg, hipMemcpyDeviceToDevice, s),
+          "copy of the order");
+  if (d_keys)
+    HIP_TRY(hipMemcpyAsync(d_keys, ord.keys, 4ull * nseg, hipMemcpyDeviceToDevice, s),
+            "copy of the keys");
+  HIP_TRY(hipGetLastError(), "order launch");
+  return 0;
 }
 
 int bitar_hip_deflate_join(bitar_hip_ctx* ctx, void* stream, const void* d_slab,

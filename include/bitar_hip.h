@@ -783,6 +783,42 @@ int bitar_hip_crc32_combine(bitar_hip_ctx* ctx, void* stream, const uint64_t* d_
 /* Whole-buffer raw Snappy streams (one stream per buffer, joined from SNAPPY segments and
  * split again on the device) have their entry points in bitar_hip_snappy.h. */
 
+/* ---- the dispatch order of a call, for tests ----
+ * Calls of at least 2048 segments run segment order[b] as workgroup b, order = the segments
+ * sorted by a cost key below 256, lowest first (larger keys count as 255; the order inside a
+ * key is not fixed).  This builds an order with the code the codecs run and copies it out.
+ *   COMPRESS_KEY    the key of LZ4 / DEFLATE / Zstd / Snappy compress: the distinct byte values
+ *                   in four 32-byte samples of each segment of d_in (n bytes, segments of seg,
+ *                   nseg = ceil(n / seg)); d_values and cut are not read: the heavy cut is the
+ *                   fast LZ4 compressor's (64) when slots != 0
+ *   DECOMPRESS_KEY  the key of their decoders, from the compressed sizes d_values[nseg] and
+ *                   seg: 255 for a size >= seg, else 254 - size * 254 / seg; d_keys must be NULL
+ *   CALLER_KEYS     d_values[nseg] are the keys
+ * cut, slots: the priority lanes of the fast LZ4 compressor.  With H = the segments whose key is
+ * below cut and S = slots, entry b carries bit 31 (which the kernel strips) iff S != 0, H > S,
+ * b < H, H % S != 0 and b % S < H % S.  slots = BITAR_HIP_ORDER_SLOTS_CALL: the S an LZ4
+ * compress call of nseg segments gets on this context and stream (0: none).  *slots_used (host
+ * memory, may be NULL) receives the S that was used.
+ * d_order (nseg words, tags left in) and d_keys (nseg words, or NULL: the keys as written,
+ * before the clamp to 255) are device memory, written in `stream`'s order.
+ * Returns 0; BITAR_HIP_NO_ORDER where a call of this context runs in plain order (nseg < 2048,
+ * BITAR_HIP_FLAG_PLAIN_ORDER, BITAR_HIP_COST_ORDER=0 in the environment, or no scratch memory):
+ * d_order and d_keys are then left alone; BITAR_HIP_INVALID for cut >= 256, nseg > 2^31, an
+ * unknown mode or a null buffer.  The keys that Zstd's and the joined Snappy decoder's
+ * internal kernels compute from scratch memory are not reachable here; their orders run
+ * through the same sort as CALLER_KEYS. */
+enum bitar_hip_order_mode {
+  BITAR_HIP_ORDER_COMPRESS_KEY = 0,
+  BITAR_HIP_ORDER_DECOMPRESS_KEY = 1,
+  BITAR_HIP_ORDER_CALLER_KEYS = 2
+};
+#define BITAR_HIP_ORDER_SLOTS_CALL 0xFFFFFFFFu
+#define BITAR_HIP_NO_ORDER 1
+int bitar_hip_debug_order(bitar_hip_ctx* ctx, void* stream, uint32_t mode, const void* d_in,
+                          uint64_t n, uint32_t seg, const uint32_t* d_values, uint32_t nseg,
+                          uint32_t cut, uint32_t slots, uint32_t* d_order, uint32_t* d_keys,
+                          uint32_t* slots_used);
+
 /* Decoder selection of one context.  The decoders are interchangeable (every one accepts and
  * rejects exactly what the oracle does); the options pick which kernels run, for tests and
  * tuning.  No reference counterpart: the BlueField engine has one decoder. */

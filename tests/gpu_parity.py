@@ -48,6 +48,31 @@ def assert_every_segment_matches_oracle(codec, data, n, seg, slab, stride, sizes
     return gs_all
 
 
+def assert_same_as_plain_order(eng, plain, codec, dcodec, data, seg):
+    """One compress of `data` (device uint8 tensor) and one decompress of its slab on each of
+    `eng` and `plain`, a BITAR_HIP_FLAG_PLAIN_ORDER context: the stride, the sizes, the live
+    bytes of every slot and the produced counts are equal, and both round trips give the input.
+    -> (eng's slab as (nseg, stride), sizes as int64 host array, live as a device mask)"""
+    import torch
+    n = data.numel()
+    nseg = (n + seg - 1) // seg
+    s1, st1, z1 = eng.compress(codec, data, seg)
+    s2, st2, z2 = plain.compress(codec, data, seg)
+    o1, p1 = eng.decompress(dcodec, s1, st1, z1, seg)
+    o2, p2 = plain.decompress(dcodec, s1, st1, z1, seg)
+    eng.sync()
+    plain.sync()
+    assert st1 == st2
+    assert torch.equal(z1, z2)
+    sizes = z1.cpu().numpy().astype(np.int64)
+    live = torch.arange(st1, device=z1.device)[None, :] < z1.to(torch.int64)[:, None]
+    a, b = s1[:nseg * st1].view(nseg, st1), s2[:nseg * st1].view(nseg, st1)
+    assert torch.equal(a * live, b * live)  # (slot bytes past a segment's size are not written)
+    assert torch.equal(p1, p2)
+    assert torch.equal(o1[:n], data) and torch.equal(o2[:n], data)
+    return a, sizes, live
+
+
 def stock_decodes_every_frame(stock_codec, slab, stride, sizes, data, n, seg):
     """Decode every GPU frame of the call with the stock library (zlib raw inflate, liblz4
     LZ4_decompress_safe, libzstd ZSTD_decompress, multi-threaded) and compare with the input."""

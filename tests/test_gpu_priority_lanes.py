@@ -13,9 +13,10 @@ Shape: 4099-byte segments (odd, no multiple of any tile) at the ordering thresho
 2049 segments, and one call of 2047 segments, which takes no order; at those sizes H stays
 under one round of resident workgroups and no entry is tagged, so one more call has H above
 a round of the fast compressor's resident workgroups (20 per CU: 5 waves per SIMD, what its
-87 VGPRs allow; big_nseg()).  The order and its tags are not visible through the C ABI, so
-what that case checks is that a call whose order carries tags changes no byte; if the
-occupancy query failed, the call would run without lanes and still pass.  Inputs: kind 1's log
+87 VGPRs allow; big_nseg()).  What an order and its tags look like -- the permutation, the keys
+along it, H, the slot count and every tagged dispatch index -- is checked by
+tests/test_gpu_order.py, which reads the orders of these pools and masks back; this file
+checks that a call whose order carries tags changes no byte.  Inputs: kind 1's log
 text (kind 6 is that region alone) for heavy segments, kind-0 random bytes for cheap ones:
 segment i of a case is segment i of one of the two pools, so the oracle's streams are
 computed once per pool and codec.
@@ -23,39 +24,25 @@ computed once per pool and codec.
 import numpy as np
 import pytest
 
+import gpu_parity as P
 import oracle_lib as O
+import order_cases as C
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SEG = 4099
-LZ4C_WAVES_PER_CU = 20  # lz4_compress_kernel<4096,10>: 5 waves per SIMD
+SEG = C.SEG
 
 
 def big_nseg():
     """the pools' size, and the tagged case's: one round of the fast compressor's resident
     workgroups on this device, and 2303 more"""
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    return LZ4C_WAVES_PER_CU * cus + 2303
+    return C.big_nseg(torch.cuda.get_device_properties(0).multi_processor_count)
 
 
 CODECS = {"LZ4": O.CODEC_LZ4, "LZ4_WIDE": O.CODEC_LZ4_WIDE}
-
-
-def masks(nseg):
-    """name -> heavy[i]: the issue's cases"""
-    i = np.arange(nseg)
-    one = i == nseg // 3
-    return {
-        "H0": np.zeros(nseg, bool),
-        "H1": one,
-        "Hn-1": ~one,
-        "Hn": np.ones(nseg, bool),
-        "half_heavy_first": i < nseg // 2,
-        "half_heavy_last": i >= nseg // 2,
-        "half_interleaved": (i & 1) == 0,
-    }
+masks = C.masks  # name -> heavy[i]: the issue's cases
 
 
 @pytest.fixture(scope="module")
@@ -78,8 +65,7 @@ def pools():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     NMAX = big_nseg()
-    text = O.fill(6, 7, NMAX * SEG)
-    rand = O.fill(0, 7, NMAX * SEG)
+    text, rand = C.lane_pools(NMAX)
     ref = {}
     for name, ocodec in CODECS.items():
         stride = bitar_amd.slot_size(getattr(bitar_amd, "CODEC_" + name), SEG)
@@ -90,7 +76,7 @@ def pools():
             ref[name].append((slab.reshape(NMAX, stride), sizes.astype(np.int64)))
     # the pools are what the cases need them to be: text is coded, random bytes are stored
     assert (ref["LZ4"][0][1] < SEG).all() and (ref["LZ4"][1][1] >= SEG).all()
-    return text.reshape(NMAX, SEG), rand.reshape(NMAX, SEG), ref
+    return text, rand, ref
 
 
 def run_case(engines, pools, codec_name, nseg, heavy):
@@ -100,21 +86,10 @@ def run_case(engines, pools, codec_name, nseg, heavy):
     codec = getattr(bitar_amd, "CODEC_" + codec_name)
     host = np.where(heavy[:, None], text[:nseg], rand[:nseg]).reshape(-1)
     data = torch.from_numpy(host).cuda()
-    s1, st1, z1 = eng.compress(codec, data, SEG)
-    s2, st2, z2 = plain.compress(codec, data, SEG)
-    o1, p1 = eng.decompress(bitar_amd.CODEC_LZ4, s1, st1, z1, SEG)
-    o2, p2 = plain.decompress(bitar_amd.CODEC_LZ4, s1, st1, z1, SEG)
-    eng.sync()
-    plain.sync()
     # against the plain-order context
-    assert st1 == st2
-    assert torch.equal(z1, z2)
-    sizes = z1.cpu().numpy().astype(np.int64)
-    live = torch.from_numpy(np.arange(st1)[None, :] < sizes[:, None]).cuda()
-    a, b = s1[:nseg * st1].view(nseg, st1), s2[:nseg * st1].view(nseg, st1)
-    assert torch.equal(a * live, b * live)  # (slot bytes past a segment's size are not written)
-    assert torch.equal(p1, p2)
-    assert torch.equal(o1[:host.size], data) and torch.equal(o2[:host.size], data)
+    a, sizes, live = P.assert_same_as_plain_order(eng, plain, codec, bitar_amd.CODEC_LZ4, data,
+                                                  SEG)
+    st1 = a.shape[1]
     # against the oracle's streams
     (tslab, tsz), (rslab, rsz) = ref[codec_name]
     assert tslab.shape[1] == st1

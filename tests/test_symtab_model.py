@@ -299,5 +299,5 @@ def test_abi_is_untouched():
     import bitar_amd as B
     import test_abi
     assert B.lib().bitar_hip_abi_version() == 3
-    assert sorted(B.ABI_SYMBOLS) == test_abi.header_symbols() and len(B.ABI_SYMBOLS) == 38
+    assert sorted(B.ABI_SYMBOLS) == test_abi.header_symbols() and len(B.ABI_SYMBOLS) == 39
     assert not [s for s in B.ABI_SYMBOLS if "symtab" in s]
