@@ -33,6 +33,8 @@ CODEC_SYMTAB = 88  # per-segment symbol table for string data (its own format, D
 #   CASCADE   RUNPACK's runs, their values and lengths packed by INTPACK (no candidate of AUTOPACK)
 #   RANSPLANE RANS with one table per byte plane of the element (likewise; width 1 is CODEC_RANS)
 #   PATCHPACK INTPACK with per-miniblock exceptions for outliers (likewise)
+#   DECPACK   INTPACK's packing for 16-byte integers, Arrow decimal128 (likewise; its id is one of
+#             the ids from 256 on, include/bitar_hip_codecs.h)
 COLUMN_CODECS = {
     "INTPACK": (8, 4, (1, 2, 4, 8)),
     "FLTPACK": (16, 5, (4, 8)),
@@ -42,6 +44,7 @@ COLUMN_CODECS = {
     "CASCADE": (64, 8, (1, 2, 4, 8)),
     "RANSPLANE": (80, 0xB, (2, 4, 8)),
     "PATCHPACK": (104, 9, (1, 2, 4, 8)),
+    "DECPACK": (256, 0xD, (16,)),
 }
 _COLUMN_IDS = {name: {w: base + w.bit_length() - 1 for w in widths}
                for name, (base, _, widths) in COLUMN_CODECS.items()}
@@ -199,8 +202,8 @@ def _column_codec(name, width):
         return _COLUMN_IDS[name][width]
     except (KeyError, TypeError):
         *most, last = map(str, COLUMN_CODECS[name][2])
-        raise ValueError(f"{name} element width must be {', '.join(most)} or {last}, "
-                         f"not {width!r}") from None
+        widths = f"{', '.join(most)} or {last}" if most else last
+        raise ValueError(f"{name} element width must be {widths}, not {width!r}") from None
 
 
 def codec_intpack(width):
@@ -236,6 +239,11 @@ def codec_cascade(width):
 def codec_patchpack(width):
     """the PATCHPACK codec id of an element width of 1, 2, 4 or 8 bytes"""
     return _column_codec("PATCHPACK", width)
+
+
+def codec_decpack(width):
+    """the DECPACK codec id of an element width of 16 bytes (Arrow decimal128)"""
+    return _column_codec("DECPACK", width)
 
 
 def codec_ransplane(width):

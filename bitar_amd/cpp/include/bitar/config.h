@@ -78,13 +78,17 @@ using Class_HIP_GFX950 =
 /// residuals that would widen a miniblock are kept raw behind the payload -- timestamps with gaps,
 /// string offsets with a long string, heavy-tailed counts, INT_MAX, 0 or -1 written for "missing";
 /// element_width() is 1, 2, 4 or 8.  No candidate of AUTOPACK.
+/// DECPACK is INTPACK's frame-of-reference bit packing for 16-byte integers (likewise its own,
+/// DESIGN.md 4.30; its id is one of the ids from 256 on, include/bitar_hip_codecs.h): Arrow
+/// decimal128 columns, whose values are a few bytes of digits under 12 or 13 bytes of sign
+/// extension; element_width() is 16.  No exceptions for outliers, no candidate of AUTOPACK.
 /// SNAPPY is one raw Snappy stream per segment: the LZ4 codec's fast parse with
 /// a Snappy emitter, readable by every stock Snappy decoder; one level, chained operations and
 /// checksums as for LZ4.
 enum class Codec : std::uint8_t {
   DEFLATE = 1, LZ4 = 2, ZSTD = 3, INTPACK = 4, FLTPACK = 5, DICTPACK = 6, RUNPACK = 7,
   AUTOPACK = 8, SNAPPY = 9, CASCADE = 10, RANS = 11, RANSPLANE = 12, SYMTAB = 13,
-  PATCHPACK = 14
+  PATCHPACK = 14, DECPACK = 15
 };
 /// rte_comp_huffman
 enum class HuffmanEncoding : std::uint8_t { DEFAULT = 0, FIXED = 1, DYNAMIC = 2 };
@@ -146,7 +150,7 @@ class Configuration {
     return compressed_seg_size_;
   }
 
-  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB and PATCHPACK have no window: Initialize
+  /// log2 of the sliding window; 0 = the device maximum.  INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB, PATCHPACK and DECPACK have no window: Initialize
   /// ignores the value and reports 0.
   [[nodiscard]] auto window_size() const noexcept { return window_size_; }
   void set_window_size(std::uint8_t window_size) { window_size_ = window_size; }
@@ -221,7 +225,7 @@ class HipConfiguration : public Configuration<Class_HIP_GFX950> {
   }
   /// The element width alone: what Codec::INTPACK (1, 2, 4 or 8 bytes), Codec::FLTPACK (4 or
   /// 8 bytes), Codec::DICTPACK (4, 8 or 16 bytes), Codec::RUNPACK and Codec::AUTOPACK (1, 2, 4,
-  /// 8 or 16 bytes), Codec::CASCADE (1, 2, 4 or 8 bytes), Codec::RANSPLANE (2, 4 or 8 bytes) and Codec::PATCHPACK (1, 2, 4 or 8 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it
+  /// 8 or 16 bytes), Codec::CASCADE (1, 2, 4 or 8 bytes), Codec::RANSPLANE (2, 4 or 8 bytes), Codec::PATCHPACK (1, 2, 4 or 8 bytes) and Codec::DECPACK (16 bytes) pack; they take no filter.  The decoder reads the width from each stream, so only the compressing side needs it
   /// -- except for Codec::RANSPLANE, whose decoder is the configured width's own and rejects
   /// streams of another width.
   void set_element_width(std::uint8_t element_width) { element_width_ = element_width; }

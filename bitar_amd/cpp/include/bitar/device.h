@@ -85,7 +85,7 @@ class CompressDevice {
   [[nodiscard]] std::uint64_t slot_size() const noexcept { return slot_size_; }
   [[nodiscard]] void* stream(std::uint16_t queue_pair_id) const;
   /// log2 of the farthest match distance the configured encoder emits (12; 14 for the wide
-  /// LZ4 parse; 0 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB and PATCHPACK, which have no matches), set by Initialize.  configuration's window_size() is what was requested (or
+  /// LZ4 parse; 0 for INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANS, RANSPLANE, SYMTAB, PATCHPACK and DECPACK, which have no matches), set by Initialize.  configuration's window_size() is what was requested (or
   /// this value when 0 was), as in the reference.
   [[nodiscard]] std::uint8_t encoder_window() const noexcept { return encoder_window_; }
 
@@ -119,7 +119,7 @@ class CompressDevice {
   }
 
   /// The element width of Codec::INTPACK, Codec::FLTPACK, Codec::DICTPACK, Codec::RUNPACK,
-  /// Codec::AUTOPACK, Codec::CASCADE, Codec::RANSPLANE and Codec::PATCHPACK, in bytes.
+  /// Codec::AUTOPACK, Codec::CASCADE, Codec::RANSPLANE, Codec::PATCHPACK and Codec::DECPACK, in bytes.
   [[nodiscard]] virtual std::uint32_t element_width() const { return 1; }
 
   [[nodiscard]] auto state() const noexcept { return state_; }

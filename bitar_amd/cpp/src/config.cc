@@ -20,6 +20,7 @@ std::string_view ToString(Codec c) {
     case Codec::RANS: return "RANS";
     case Codec::RANSPLANE: return "RANSPLANE";
     case Codec::PATCHPACK: return "PATCHPACK";
+    case Codec::DECPACK: return "DECPACK";
     case Codec::SYMTAB: return "SYMTAB";
   }
   return "UNKNOWN";

@@ -18,6 +18,7 @@
 
 #include "bitar/hip_device.h"
 #include "bitar_hip.h"
+#include "bitar_hip_codecs.h"
 #include "hip_ctx.h"
 
 namespace bitar {
@@ -305,7 +306,8 @@ constexpr ColumnCodec kColumnCodecs[] = {{Codec::INTPACK, "INTPACK", 1 | 2 | 4 |
                                          {Codec::AUTOPACK, "AUTOPACK", 1 | 2 | 4 | 8 | 16},
                                          {Codec::CASCADE, "CASCADE", 1 | 2 | 4 | 8},
                                          {Codec::RANSPLANE, "RANSPLANE", 2 | 4 | 8},
-                                         {Codec::PATCHPACK, "PATCHPACK", 1 | 2 | 4 | 8}};
+                                         {Codec::PATCHPACK, "PATCHPACK", 1 | 2 | 4 | 8},
+                                         {Codec::DECPACK, "DECPACK", 16}};
 
 const ColumnCodec* FindColumnCodec(Codec codec) {
   for (const auto& c : kColumnCodecs)
@@ -328,7 +330,7 @@ std::string WidthList(std::uint32_t widths) {
 
 // DEFLATE + FIXED -> fixed-Huffman blocks; DEFLATE + DYNAMIC (the reference default,
 // config.h:151) or DEFAULT (the PMD's choice) -> dynamic Huffman
-// INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANSPLANE, PATCHPACK -> the id of the configured element width
+// INTPACK, FLTPACK, DICTPACK, RUNPACK, AUTOPACK, CASCADE, RANSPLANE, PATCHPACK, DECPACK -> the id of the configured element width
 template <typename Cfg>
 std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
   switch (c.codec()) {
@@ -340,6 +342,7 @@ std::uint32_t AbiCodec(const Cfg& c, std::uint32_t element_width) {
     case Codec::CASCADE: return BITAR_HIP_CODEC_CASCADE(element_width);
     case Codec::RANSPLANE: return BITAR_HIP_CODEC_RANSPLANE(element_width);
     case Codec::PATCHPACK: return BITAR_HIP_CODEC_PATCHPACK(element_width);
+    case Codec::DECPACK: return BITAR_HIP_CODEC_DECPACK(element_width);
     case Codec::LZ4: return c.level() >= 2 ? BITAR_HIP_CODEC_LZ4_WIDE : BITAR_HIP_CODEC_LZ4;
     case Codec::ZSTD: return BITAR_HIP_CODEC_ZSTD;
     case Codec::SNAPPY: return BITAR_HIP_CODEC_SNAPPY;

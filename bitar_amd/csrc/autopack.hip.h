@@ -1,5 +1,5 @@
 // autopack.hip.h -- what the column codecs' files (intpack.hip, fltpack.hip, dictpack.hip,
-// runpack.hip, cascade.hip, patchpack.hip) share: the kernels around a format's compress_segment and
+// runpack.hip, cascade.hip, patchpack.hip, decpack.hip) share: the kernels around a format's compress_segment and
 // decode_stream, the frame every stream starts with, and which segment a workgroup of one of
 // AUTOPACK's LISTED decoders takes (autopack.hip).
 //
@@ -29,6 +29,7 @@ struct Rans;       // (rans.hip)
 struct RansPlane;  // (ransplane.hip; a decoder per element width)
 template <uint32_t W> struct RansPlaneDecoder;
 struct SymTab;     // (symtab.hip)
+struct DecPack;    // (decpack.hip; ids from 256 on, include/bitar_hip_codecs.h)
 
 // Segment i: min(seg, n_total - i*seg) bytes at input + i*seg -> its slot (slab + i*slot_stride,
 // or dsts[i]); sizes[i] = the stream's size (at most 4 + the segment's length: never a failure).

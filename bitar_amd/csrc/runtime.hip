@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/bitar_hip.h"
+#include "../../include/bitar_hip_codecs.h"
 #include "../../include/bitar_hip_snappy.h"
 #define BITAR_COLUMN_DECLARATIONS_ONLY  // (the kernels are defined in the formats' files)
 #include "autopack.hip.h"
@@ -266,7 +267,7 @@ extern "C++" {
 // The column codecs: a family's ids are base + log2(element width) for the widths it offers
 // (`widths`: those widths ORed together, so bit lg stands for 1 << lg bytes), and its streams
 // carry `nibble` in the high half of byte 0
-// (AUTOPACK has no format of its own).  CASCADE, RANSPLANE, PATCHPACK, RANS and SYMTAB are no
+// (AUTOPACK has no format of its own).  CASCADE, RANSPLANE, PATCHPACK, RANS, SYMTAB and DECPACK are no
 // candidates of AUTOPACK: they have no store-less encoder and no listed decoder, and they come
 // after the families that do.  RANS and SYMTAB are byte codecs run by the column kernels: one id
 // each, width 1.  Two orders here are load-bearing:
@@ -278,7 +279,7 @@ extern "C++" {
 //     writes.
 enum ColumnFamily : int {
   kIntPack, kFltPack, kDictPack, kRunPack, kAutoPack, kCascade, kRansPlane, kPatchPack, kRans,
-  kSymTab, kColumnFamilies
+  kSymTab, kDecPack, kColumnFamilies
 };
 struct ColumnRow {
   uint32_t base, nibble, widths;
@@ -294,6 +295,7 @@ constexpr ColumnRow kColumn[kColumnFamilies] = {
     {BITAR_HIP_CODEC_PATCHPACK8, 9, 1 | 2 | 4 | 8},          // PATCHPACK (likewise)
     {BITAR_HIP_CODEC_RANS, 0xA, 1},                          // RANS (likewise; bytes)
     {BITAR_HIP_CODEC_SYMTAB, 0xC, 1},                        // SYMTAB (likewise; bytes)
+    {BITAR_HIP_CODEC_DECPACK128 - 4, 0xD, 16},               // DECPACK (likewise; bitar_hip_codecs.h)
 };
 constexpr ColumnFamily kCandidates[] = {kRunPack, kIntPack, kDictPack, kFltPack};
 constexpr uint32_t kListedDecoders = 4;
@@ -347,6 +349,7 @@ static CompressKernel compress_kernel(ColumnFamily f, uint32_t lg) {
     case kPatchPack: return width_kernel<bitar_hip::PatchPack, kPatchPack, true>(lg);
     case kRans: return width_kernel<bitar_hip::Rans, kRans, true>(lg);
     case kSymTab: return width_kernel<bitar_hip::SymTab, kSymTab, true>(lg);
+    case kDecPack: return width_kernel<bitar_hip::DecPack, kDecPack, true>(lg);
     default: return nullptr;
   }
 }
@@ -369,6 +372,7 @@ static DecompressKernel decompress_kernel(uint32_t f, uint32_t lg) {
       case kPatchPack: return column_decompress_kernel<PatchPack, false>;
       case kRans: return column_decompress_kernel<Rans, false>;
       case kSymTab: return column_decompress_kernel<SymTab, false>;
+      case kDecPack: return column_decompress_kernel<DecPack, false>;
       case kRansPlane:
         switch (lg) {
           case 1: return column_decompress_kernel<RansPlaneDecoder<2>, false>;
@@ -647,7 +651,7 @@ extern "C" __attribute__((visibility("default"))) uint32_t bitar_hip_timeline_sl
 
 // A family's codec: one streaming kernel, the same work for every segment: plain order
 // (intpack.hip, fltpack.hip, dictpack.hip, runpack.hip, cascade.hip, ransplane.hip,
-// patchpack.hip, and the byte codecs rans.hip and symtab.hip: one segment's histogram or table,
+// patchpack.hip, decpack.hip, and the byte codecs rans.hip and symtab.hip: one segment's histogram or table,
 // and its coder, in one wave).  A segment never fails (the stored form fits every slot).
 // AUTOPACK: the smallest of the candidates' streams per segment (autopack.hip): RUNPACK straight
 // into the caller's slots, every later candidate that offers the width (kCandidates, kColumn)

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/../bitar_amd"
 name=$1; defs=$2
 mkdir -p build_$name lib/variants
-for f in runtime lz4_decompress inflate inflate_fixed compress util_kernels zstd_decompress zstd_compress zstd_lanes inflate_lanes deflate_dyn checksum lz4_chain zstd_seq deflate_join filter intpack fltpack dictpack runpack autopack snappy cascade rans ransplane symtab patchpack; do
+for f in runtime lz4_decompress inflate inflate_fixed compress util_kernels zstd_decompress zstd_compress zstd_lanes inflate_lanes deflate_dyn checksum lz4_chain zstd_seq deflate_join filter intpack fltpack dictpack runpack autopack snappy cascade rans ransplane symtab patchpack decpack; do
   extra=""
   case $f in  # (the Makefile's per-file scheduler; FLAGS_<file> below overrides)
     lz4_decompress) extra="-mllvm -amdgpu-sched-strategy=max-ilp";;
