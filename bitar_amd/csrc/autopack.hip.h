@@ -1,7 +1,9 @@
 // autopack.hip.h -- what the column codecs' files (intpack.hip, fltpack.hip, dictpack.hip,
-// runpack.hip, cascade.hip, patchpack.hip, decpack.hip) share: the kernels around a format's compress_segment and
-// decode_stream, the frame every stream starts with, and which segment a workgroup of one of
-// AUTOPACK's LISTED decoders takes (autopack.hip).
+// runpack.hip, cascade.hip, patchpack.hip, decpack.hip) share: the kernels around a format's
+// compress_segment and decode_stream, the frame every stream starts with, and which segment a
+// workgroup of one of AUTOPACK's LISTED decoders takes (autopack.hip).
+// (What the bit-packing formats share below that, INTPACK's and DECPACK's whole segment encoder
+// and decoder included, is in bitpack.hip.h.)
 //
 // A format is a traits type F, defined in the format's own file:
 //   F::kNibble                          the high nibble of byte 0 of its streams

@@ -126,7 +126,7 @@ __device__ __forceinline__ void compress_segment(const GMEM uint8_t* src, uint32
         uint32_t B;
         if (md == 2) {
           r = idx < m ? (U)(((U)~p.x[0][j] - ref) & mask) : (U)0;
-          B = bit_length(wave_or<U>(r));
+          B = wave_width<W>(r);
         } else {
           r = p.residual(md, j, idx < m);
           B = p.b[md][j];
